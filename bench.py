@@ -9,6 +9,13 @@ frame-pair stream per rank, synthetic data, random-init weights).
   # N>1 is launched by the driver via torch.distributed.run (one rank/GPU,
   # RCCL over xGMI); rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the result
+line. --dump-outputs DIR also writes what the last timed step returned
+(the flow field; loss/epe/lr for --train) as DIR/<name>.npy, so two builds
+can be compared output for output: model weights and inputs are seeded and
+identical from run to run. --full is where anything beyond the headline
+figure belongs; nothing does at present.
+
 Extra modes (not used by the driver contract): --train benches the DP
 training step (config 3 shape), --small / --height/--width/--iters override
 the model/config.
@@ -42,7 +49,54 @@ def parse_args():
     p.add_argument("--trace-table", action="store_true",
                    help="print a torch-profiler op table of 3 steps to "
                         "stderr (works for --train too)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step returned as DIR/<name>.npy (rank 0)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary sections; a "
+                        "plain run only times the headline steps (there "
+                        "are no secondary sections at present)")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def _named_outputs(out, train):
+    """The last timed step's return value as {name: float ndarray}."""
+    import numpy as np
+    if isinstance(out, torch.Tensor):
+        out = {"loss" if train else "flow": out}
+    elif isinstance(out, (list, tuple)):
+        out = {f"out{i}": v for i, v in enumerate(out)}
+    arrays = {}
+    for name, v in out.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach()
+            v = v.to("cpu", torch.float64 if v.dtype == torch.float64
+                     else torch.float32).numpy()
+        a = np.asarray(v)
+        if a.dtype != np.float64:
+            a = a.astype(np.float32)
+        arrays[name] = a
+    return arrays
+
+
+def dump_outputs(out, path, train=False):
+    """Write the step's outputs as <path>/<name>.npy (float32/float64),
+    at most DUMP_BUDGET_BYTES in all: an array over its share of the
+    budget is stored as a fixed seeded sample of its flattened elements
+    (the same positions every run, in ascending order)."""
+    import numpy as np
+    arrays = _named_outputs(out, train)
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            rng = np.random.default_rng(0)
+            idx = np.sort(rng.integers(0, a.size, share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def pad8(x):
@@ -162,9 +216,11 @@ def main():
                   file=sys.stderr)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        run_step()
+        out = run_step()
     sync()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs, train=args.train)
 
     if dist is not None:
         t = torch.tensor([elapsed], device=dev if have_gpu else "cpu")

@@ -63,6 +63,7 @@ def build_native(verbose: bool = False) -> Optional[str]:
     if not os.path.exists(src):
         return None
     for cc in ("cc", "gcc", "clang"):
+        tmp = None          # stays None when the tree is not writable
         try:
             with tempfile.NamedTemporaryFile(
                     dir=_CSRC, suffix=".so", delete=False) as tf:
@@ -78,7 +79,8 @@ def build_native(verbose: bool = False) -> Optional[str]:
             os.unlink(tmp)
         except (OSError, subprocess.TimeoutExpired):
             try:
-                os.unlink(tmp)
+                if tmp is not None:
+                    os.unlink(tmp)
             except OSError:
                 pass
             continue

@@ -94,10 +94,13 @@ def test_png_decoder_on_system_files():
     """Real-world PNGs written by external tools (sub-byte bit depths
     are the only rejected class — loudly)."""
     import glob as _glob
+    import os
     from raft_amd.data.imageio import decode_png
-    candidates = sorted(_glob.glob("/usr/share/gitweb/static/*.png")) + \
-        sorted(_glob.glob("/usr/share/icons/ubuntu-mono-light/stock/64/"
-                          "*.png"))[:5]
+    # copies of gitweb / desktop-icon PNGs, stored with the tests
+    candidates = sorted(_glob.glob(os.path.join(
+        os.path.dirname(os.path.abspath(__file__)), "golden", "images",
+        "*.png")))
+    assert len(candidates) == 3, candidates
     checked = 0
     for path in candidates[:8]:
         data = open(path, "rb").read()

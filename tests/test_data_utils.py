@@ -10,6 +10,8 @@ from raft_amd.utils.flow_io import read_flo, write_flo, resize_flow
 from raft_amd.utils.flow_viz import flow_to_color, make_colorwheel
 from raft_amd.engine.inference import pad8, unpad, InferenceEngine
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
 
 def test_png_roundtrip(tmp_path):
     img = (np.random.rand(37, 53, 3) * 255).astype(np.uint8)
@@ -415,7 +417,7 @@ def test_train_mode_file_based(tmp_path):
         [sys.executable, "infer_raft.py", "--mode", "train", "--small",
          "--steps", "2", "--batch", "1", "--data", str(tmp_path),
          "--out", str(out)],
-        capture_output=True, text=True, cwd="/root/repo", timeout=600)
+        capture_output=True, text=True, cwd=REPO, timeout=600)
     assert r.returncode == 0, r.stderr[-800:]
     assert "training on" in r.stdout and "3 triplets" in r.stdout
     assert (out / "raft_trained.npz").exists()
@@ -613,7 +615,7 @@ def test_cli_warm_native_non_divisible(tmp_path):
         [sys.executable, "infer_raft.py", "--mode", "test", "--small",
          "--data", str(tmp_path), "--size", "native", "--warm",
          "--iters", "2", "--out", str(tmp_path / "o")],
-        capture_output=True, text=True, cwd="/root/repo", timeout=600)
+        capture_output=True, text=True, cwd=REPO, timeout=600)
     assert r.returncode == 0, r.stderr[-800:]
     assert "(1, 2, 30, 44)" in r.stdout
 
@@ -676,8 +678,9 @@ def test_cli_missing_file_clean_error(tmp_path):
     import sys
     r = subprocess.run(
         [sys.executable, "infer_raft.py", "--mode", "test", "--small",
-         "--im1", "/nope/a.png", "--im2", "/nope/b.png", "--iters", "1"],
-        capture_output=True, text=True, cwd="/root/repo", timeout=300)
+         "--im1", "/nope/a.png", "--im2", "/nope/b.png", "--iters", "1",
+         "--out", str(tmp_path / "o")],
+        capture_output=True, text=True, cwd=REPO, timeout=300)
     assert r.returncode != 0
     assert "file not found" in r.stderr
     assert "Traceback" not in r.stderr

@@ -93,12 +93,25 @@ def _run_bench_train(rank, world, port):
 
 
 def test_trainer_distributed_steps():
+    """Two gloo ranks step the Trainer on CPU. The spawned ranks inherit
+    an environment with no visible GPU: this is the CPU path's test, and
+    two ranks must not both land on device 0 of a one-GPU machine."""
     ctx = mp.get_context("spawn")
     port = 29613
     procs = [ctx.Process(target=_run_bench_train, args=(r, 2, port))
              for r in range(2)]
-    for p in procs:
-        p.start()
+    hide = ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")
+    saved = {k: os.environ.get(k) for k in hide}
+    os.environ.update({k: "" for k in hide})
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
     for p in procs:
         p.join(300)
         assert p.exitcode == 0

@@ -18,14 +18,12 @@ from raft_amd.data.jpeg import decode_jpeg, encode_jpeg
 
 PIL = pytest.importorskip("PIL.Image")
 
-SYSTEM_JPEGS = [p for p in [
-    "/usr/local/lib/python3.10/dist-packages/matplotlib/mpl-data/"
-    "sample_data/grace_hopper.jpg",
-    "/usr/local/lib/python3.10/dist-packages/sklearn/datasets/images/"
-    "china.jpg",
-    "/usr/local/lib/python3.10/dist-packages/sklearn/datasets/images/"
-    "flower.jpg",
-] if os.path.exists(p)]
+GOLDEN_IMAGES = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                             "golden", "images")
+# libjpeg-written sample photographs (matplotlib / scikit-learn sample
+# data), stored with the tests so the suite needs nothing outside the repo
+SYSTEM_JPEGS = [os.path.join(GOLDEN_IMAGES, n) for n in (
+    "grace_hopper.jpg", "china.jpg", "flower.jpg")]
 
 
 def _pil_bgr(src) -> np.ndarray:
