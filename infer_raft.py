@@ -7,7 +7,8 @@ Modes:
   test    run flow on an image pair — or consecutive pairs of a --data
           directory (--warm warm-starts, --workers parallel decode) —
           and write the color-coded PNG (reference infer_raft.py:74-78;
-          output file name kept)
+          output file name kept); --bidirectional adds the backward flow
+          and forward-backward occlusion masks from the same pass
   train   train on synthetic pairs, or on a --data directory of flow
           triplets (Sintel dir/tree, KITTI devkit, FlyingChairs);
           preemption-safe (--resume, --save-every, SIGTERM), --accum
@@ -20,9 +21,9 @@ Modes:
 
 Flags mirror the reference (infer_raft.py:51-67): --gpu --data --load
 -m/--mode --out --batch -o/--optimizer --im1 --im2 --small, plus the
-rebuild's --iters/--size/--dtype/--steps/--warm/--workers/--resume/
---save-every/--accum (iters was hard-coded 20 in the reference,
-networks/RAFT.py:33).
+rebuild's --iters/--size/--dtype/--steps/--warm/--bidirectional/
+--workers/--resume/--save-every/--accum (iters was hard-coded 20 in the
+reference, networks/RAFT.py:33).
 """
 import argparse
 import json
@@ -67,6 +68,10 @@ def parse_args(argv=None):
     p.add_argument("--warm", action="store_true",
                    help="warm-start each sequence pair from the previous "
                         "flow (official-RAFT 2-view style)")
+    p.add_argument("--bidirectional", action="store_true",
+                   help="test mode: also compute the backward flow and "
+                        "forward-backward occlusion masks in the same pass "
+                        "(writes *_bw.flo/.png and raft_occ_*_{fw,bw}.png)")
     p.add_argument("--workers", type=int, default=0,
                    help="parallel decode workers for sequence/val modes")
     p.add_argument("--resume", action="store_true",
@@ -143,20 +148,33 @@ def mode_test(args, device):
     os.makedirs(args.out, exist_ok=True)
     variant = "raft-small" if args.small else "raft-things"
     prev_flow = None
+    prev_bw = None
+
+    def _warm(prev):
+        import torch.nn.functional as Fn
+        # the engine pads frames up to a multiple of 8, so the model's
+        # coords grid is ceil(H/8) x ceil(W/8) — match that here or
+        # 'coords1 + flow_init' shape-mismatches on e.g. 436-high frames
+        h8 = -(-prev.shape[-2] // 8)
+        w8 = -(-prev.shape[-1] // 8)
+        return Fn.interpolate(prev, size=(h8, w8), mode="bilinear",
+                              align_corners=False) / 8.0
+
     for i, (im1, im2) in enumerate(ds):
         flow_init = None
         if args.warm and prev_flow is not None:
-            import torch.nn.functional as Fn
-            # the engine pads frames up to a multiple of 8, so the model's
-            # coords grid is ceil(H/8) x ceil(W/8) — match that here or
-            # 'coords1 + flow_init' shape-mismatches on e.g. 436-high frames
-            h8 = -(-prev_flow.shape[-2] // 8)
-            w8 = -(-prev_flow.shape[-1] // 8)
-            flow_init = Fn.interpolate(prev_flow, size=(h8, w8),
-                                       mode="bilinear",
-                                       align_corners=False) / 8.0
+            flow_init = _warm(prev_flow)
+            if args.bidirectional:
+                # each direction warm-starts from its own previous flow
+                flow_init = (flow_init, _warm(prev_bw))
         t0 = time.perf_counter()
-        flow = engine(im1, im2, flow_init=flow_init)
+        bidir = None
+        if args.bidirectional:
+            bidir = engine.bidirectional(im1, im2, flow_init=flow_init)
+            flow = bidir.flow_fw
+            prev_bw = bidir.flow_bw.float()
+        else:
+            flow = engine(im1, im2, flow_init=flow_init)
         prev_flow = flow.float()
         if device.type == "cuda":
             torch.cuda.synchronize()
@@ -176,6 +194,18 @@ def mode_test(args, device):
             write_flo(os.path.join(
                 args.out, f"raft_flow_{variant}{suffix}.flo"), flow_np)
             print(f"wrote {out_path}")
+            if bidir is not None:
+                stem = os.path.join(args.out, f"raft_flow_{variant}{suffix}")
+                bw_np = bidir.flow_bw[j].float().permute(1, 2, 0) \
+                    .cpu().numpy()
+                write_png(stem + "_bw.png",
+                          flow_to_color(bw_np, convert_to_bgr=True))
+                write_flo(stem + "_bw.flo", bw_np)
+                occ = os.path.join(args.out, f"raft_occ_{variant}{suffix}")
+                for tag, m in (("fw", bidir.occ_fw), ("bw", bidir.occ_bw)):
+                    write_png(f"{occ}_{tag}.png",
+                              m[j, 0].cpu().numpy().astype(np.uint8) * 255)
+                print(f"wrote {stem}_bw.png and {occ}_fw.png / _bw.png")
 
 
 def mode_val(args, device):

@@ -10,7 +10,7 @@ and cached by (B, H, W) bucket, removing the ~1000-launch overhead of the
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -30,6 +30,15 @@ def pad8(x: torch.Tensor) -> Tuple[torch.Tensor, Tuple[int, int]]:
 def unpad(flow: torch.Tensor, hw: Tuple[int, int]) -> torch.Tensor:
     h, w = hw
     return flow[..., :h, :w]
+
+
+class BidirectionalFlow(NamedTuple):
+    """Result of InferenceEngine.bidirectional: flows [B,2,H,W] and
+    occlusion masks [B,1,H,W] bool (True = occluded)."""
+    flow_fw: torch.Tensor
+    flow_bw: torch.Tensor
+    occ_fw: torch.Tensor
+    occ_bw: torch.Tensor
 
 
 class InferenceEngine:
@@ -76,9 +85,11 @@ class InferenceEngine:
     @torch.no_grad()
     def __call__(self, image1: torch.Tensor, image2: torch.Tensor,
                  iters: Optional[int] = None,
-                 flow_init: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 flow_init=None, bidirectional: bool = False):
         """flow_init: [B,2,H/8,W/8] warm-start at 1/8 resolution (official
-        RAFT 2-view warm start; the BASELINE EPE anchor is quoted with it)."""
+        RAFT 2-view warm start; the BASELINE EPE anchor is quoted with it).
+        bidirectional=True returns the unpadded pair (flow_fw, flow_bw)
+        from one shared pass; flow_init is then None or a pair."""
         iters = iters if iters is not None else self.iters
         image1 = image1.to(self.device, self.dtype, non_blocking=True)
         image2 = image2.to(self.device, self.dtype, non_blocking=True)
@@ -88,11 +99,19 @@ class InferenceEngine:
             image1 = image1.contiguous(memory_format=torch.channels_last)
             image2 = image2.contiguous(memory_format=torch.channels_last)
         from raft_amd.models import fused
-        if fused.can_fuse(self.model, image1):
+        fusable = fused.can_fuse(self.model, image1)
+        if fusable:
             # fused path: loop_graph None = AUTO (the fused loop captures
             # at iters <= 16, runs eager above — replay serializes the
             # two-stream overlap that pays at long iteration counts)
             self.model._fused_use_graph = self.loop_graph
+        if bidirectional:
+            # off the fused path this skips whole-model graph capture, as
+            # flow_init calls do
+            fw, bw = self.model(image1, image2, iters=iters,
+                                flow_init=flow_init, bidirectional=True)
+            return unpad(fw, hw), unpad(bw, hw)
+        if fusable:
             return unpad(self.model(image1, image2, iters=iters,
                                     flow_init=flow_init), hw)
         if not self.use_graph or flow_init is not None:
@@ -114,6 +133,21 @@ class InferenceEngine:
         in2.copy_(image2)
         graph.replay()
         return unpad(out, hw)
+
+    @torch.no_grad()
+    def bidirectional(self, image1: torch.Tensor, image2: torch.Tensor,
+                      iters: Optional[int] = None, flow_init=None,
+                      alpha1: float = 0.01, alpha2: float = 0.5
+                      ) -> BidirectionalFlow:
+        """Both flows plus forward-backward occlusion masks. The masks are
+        computed on the unpadded flows, so "leaves the frame" means the
+        real frame, not the pad8 canvas."""
+        from raft_amd import ops
+        fw, bw = self(image1, image2, iters=iters, flow_init=flow_init,
+                      bidirectional=True)
+        occ_fw, occ_bw = ops.fb_consistency(fw.contiguous(), bw.contiguous(),
+                                            alpha1, alpha2)
+        return BidirectionalFlow(fw, bw, occ_fw, occ_bw)
 
     def _capture(self, image1, image2, iters):
         in1 = image1.clone()

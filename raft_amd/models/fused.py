@@ -377,6 +377,9 @@ class FusedEncoder:
         return self.proj(hip, h, ACT_NONE)
 
 
+_warned_bidir_fp8 = False
+
+
 class FusedRaft:
     """Caches packed weights for a RAFT model; call run() for inference."""
 
@@ -448,7 +451,13 @@ class FusedRaft:
         return hip.convex_upsample(flow_nchw, mask_nchw)
 
     @torch.no_grad()
-    def run(self, image1, image2, iters, flow_init=None):
+    def run(self, image1, image2, iters, flow_init=None,
+            bidirectional=False):
+        """bidirectional: both directions share one pass — cnet sees both
+        frames, the volume kernel stores each tile twice (forward and
+        transposed) and the loop runs at batch 2B ([fw | bw]); flow_init
+        is then already the [2B,2,H8,W8] concatenation. Returns the pair
+        (flow_fw, flow_bw)."""
         model = self.model
         cfg = model.cfg
         hip = self.hip
@@ -471,7 +480,8 @@ class FusedRaft:
             x8[B0:, ..., :3] = img2.permute(0, 2, 3, 1)
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                cnet_p = self.cnet_f(hip, x8[:B0].contiguous())
+                cnet_p = self.cnet_f(hip, x8 if bidirectional
+                                     else x8[:B0].contiguous())
             fmaps_p = self.fnet_f(hip, x8)
             f1p = fmaps_p[:B0].contiguous()
             f2p = fmaps_p[B0:].contiguous()
@@ -482,7 +492,8 @@ class FusedRaft:
             f2p = fmap2.permute(0, 2, 3, 1).contiguous()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                cnet = model.cnet(img1)
+                cnet = model.cnet(torch.cat([img1, img2], dim=0)
+                                  if bidirectional else img1)
         B, H8, W8, C = f1p.shape
 
         import os as _os
@@ -490,7 +501,21 @@ class FusedRaft:
         if C % 128 != 0:
             fp8_mode = "0"
         self._vol_scale = None
-        if fp8_mode == "2":
+        if bidirectional:
+            if fp8_mode != "0":
+                global _warned_bidir_fp8
+                if not _warned_bidir_fp8:
+                    _warned_bidir_fp8 = True
+                    import warnings
+                    warnings.warn("RAFT_AMD_FP8_CORR is ignored for "
+                                  "bidirectional runs: using the bf16 "
+                                  "correlation volume")
+            # [2B, HW, H8, W8]: forward volume, then its exact transpose
+            # (= the volume of (f2, f1)) from the same accumulators
+            vol = hip.corr_volume_nhwc_bidir(f1p, f2p)
+            pool = hip.corr_pool2x_bf16
+            B = 2 * B
+        elif fp8_mode == "2":
             # r2 roadmap #4: e4m3 GEMM AND e4m3 volume storage — halves
             # the volume write/read streams; lookup dequantizes by the
             # device-scalar vol_scale
@@ -546,17 +571,25 @@ class FusedRaft:
             x_buf = torch.empty(B, H8, W8, self.x_dim, device=net.device,
                                 dtype=torch.bfloat16)
             x_buf[..., :cfg.context_dim] = inp
-            return self._loop(levels, net, x_buf, coords0, coords1, iters)
+            out = self._loop(levels, net, x_buf, coords0, coords1, iters)
+            return (out[:B // 2], out[B // 2:]) if bidirectional else out
 
+        # a bidirectional run shares the captured loop of a unidirectional
+        # batch-2B run (identical kernels) — except under RAFT_AMD_FP8_CORR,
+        # where that graph may hold fp8 level buffers
         key = (B, H8, W8, iters)
+        if bidirectional and fp8_mode != "0":
+            key += ("bf16",)
         entry = self._graphs.get(key)
         if entry is None:
             if len(self._graphs) >= 4:     # shape-bucket cap
                 x_buf = torch.empty(B, H8, W8, self.x_dim,
                                     device=net.device, dtype=torch.bfloat16)
                 x_buf[..., :cfg.context_dim] = inp
-                return self._loop(levels, net, x_buf, coords0, coords1,
-                                  iters)
+                out = self._loop(levels, net, x_buf, coords0, coords1,
+                                 iters)
+                return (out[:B // 2], out[B // 2:]) if bidirectional \
+                    else out
             entry = self._capture(levels, net, inp, coords0, coords1, iters)
             self._graphs[key] = entry
         graph, st = entry
@@ -568,7 +601,8 @@ class FusedRaft:
         if st.get("vol_scale") is not None:   # fp8-storage dequant scalar
             st["vol_scale"].copy_(self._vol_scale)
         graph.replay()
-        return st["out"]
+        out = st["out"]
+        return (out[:B // 2], out[B // 2:]) if bidirectional else out
 
     def _capture(self, levels, net, inp, coords0, coords1, iters):
         cfg = self.model.cfg

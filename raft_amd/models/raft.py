@@ -97,7 +97,7 @@ class RAFT(nn.Module):
     # ------------------------------------------------------------------
     def forward(self, image1: torch.Tensor, image2: torch.Tensor,
                 iters: Optional[int] = None, flow_init: Optional[torch.Tensor] = None,
-                test_mode: bool = True):
+                test_mode: bool = True, bidirectional: bool = False):
         """Run the recurrent refinement.
 
         image1/image2: [B, 3, H, W] BGR in [0,1] (H, W divisible by 8 —
@@ -106,10 +106,26 @@ class RAFT(nn.Module):
         the list of per-iteration upsampled flow predictions (for the
         sequence loss — designed from the RAFT paper; the reference has no
         training path).
+
+        bidirectional=True (test_mode only) returns ``(flow_fw, flow_bw)``
+        — image1->image2 and image2->image1 — from ONE shared pass: fnet
+        already sees both frames, the backward correlation volume is the
+        transpose of the forward one, and the loop runs both directions
+        as one batch of 2B. flow_init is then None or ``(init_fw, init_bw)``.
         """
         iters = iters if iters is not None else self.cfg.iters
         if iters < 1:
             raise ValueError(f"iters must be >= 1, got {iters}")
+        if bidirectional:
+            if not test_mode:
+                raise ValueError("bidirectional=True needs test_mode=True "
+                                 "(training is unidirectional)")
+            if flow_init is not None:
+                if not (isinstance(flow_init, (tuple, list))
+                        and len(flow_init) == 2):
+                    raise ValueError("bidirectional flow_init must be None "
+                                     "or a pair (init_fw, init_bw)")
+                flow_init = torch.cat([flow_init[0], flow_init[1]], dim=0)
 
         # MI355X fast path: whole refinement loop on the fused NHWC bf16
         # kernels (inference only; numerics-tested vs this eager path).
@@ -117,7 +133,7 @@ class RAFT(nn.Module):
             from raft_amd.models import fused
             if fused.can_fuse(self, image1):
                 return fused.get_fused(self).run(image1, image2, iters,
-                                                 flow_init)
+                                                 flow_init, bidirectional)
 
         img1 = self.preprocess(image1)
         img2 = self.preprocess(image2)
@@ -126,6 +142,10 @@ class RAFT(nn.Module):
         # (reference shares via tf.AUTO_REUSE, model_utils.py:69)
         fmaps = self.fnet(torch.cat([img1, img2], dim=0))
         fmap1, fmap2 = torch.chunk(fmaps, 2, dim=0)
+        if bidirectional:
+            # both directions as one batch of 2B: [fw | bw]
+            fmap1, fmap2 = fmaps, torch.cat([fmap2, fmap1], dim=0)
+            img1 = torch.cat([img1, img2], dim=0)
 
         pyramid = ops.corr_pyramid(fmap1, fmap2, self.cfg.corr_levels)
 
@@ -164,7 +184,11 @@ class RAFT(nn.Module):
 
         if not test_mode:
             return flow_predictions
-        return self._upsample(coords1 - coords0, up_mask)
+        up = self._upsample(coords1 - coords0, up_mask)
+        if bidirectional:
+            B = image1.shape[0]
+            return up[:B], up[B:]
+        return up
 
     def _upsample(self, flow: torch.Tensor, up_mask: Optional[torch.Tensor]):
         if self.cfg.small:

@@ -63,6 +63,11 @@ void launch_fconv_fp8_gru(const void*, int, const void*, int, const void*,
                           void*, void*, hipStream_t);
 void launch_corr_volume_nhwc_bf16(const void*, const void*, void*, bool,
                                   int, int, int, int, float, hipStream_t);
+void launch_corr_volume_nhwc_bidir(const void*, const void*, void*, int, int,
+                                   int, float, hipStream_t);
+void launch_fb_consistency(const void*, const void*, unsigned char*, float*,
+                           float*, int, int, int, int, float, float,
+                           hipStream_t);
 void launch_corr_lookup_nhwc(const void* const*, const int*, const int*,
                              int, const float*, const float*, void*, bool,
                              void*, int, int, int, int, int, int, int, int,
@@ -377,6 +382,61 @@ at::Tensor corr_volume_nhwc(at::Tensor f1, at::Tensor f2, bool out_bf16) {
                                  1.0f / std::sqrt((float)C),
                                  current_stream());
     return out;
+}
+
+at::Tensor corr_volume_nhwc_bidir(at::Tensor f1, at::Tensor f2) {
+    // both directions from one GEMM: out[:B] is corr_volume_nhwc(f1, f2)
+    // (bf16), out[B:] its exact transpose == the volume of (f2, f1)
+    CHECK_DEV(f1); CHECK_CONT(f1); CHECK_DEV(f2); CHECK_CONT(f2);
+    TORCH_CHECK(f1.scalar_type() == at::kBFloat16 &&
+                f2.scalar_type() == at::kBFloat16, "nhwc volume needs bf16");
+    TORCH_CHECK(f1.dim() == 4 && f1.sizes() == f2.sizes());
+    const int B = f1.size(0), H = f1.size(1), W = f1.size(2), C = f1.size(3);
+    TORCH_CHECK(C % 64 == 0, "C must be a multiple of 64");
+    const int M = H * W;
+    auto out = at::empty({2 * (int64_t)B, M, H, W}, f1.options());
+    if (out.numel() == 0) return out;
+    launch_corr_volume_nhwc_bidir(f1.data_ptr(), f2.data_ptr(),
+                                  out.data_ptr(), B, M, C,
+                                  1.0f / std::sqrt((float)C),
+                                  current_stream());
+    return out;
+}
+
+std::vector<at::Tensor> fb_consistency(at::Tensor flow_fw, at::Tensor flow_bw,
+                                       double alpha1, double alpha2,
+                                       bool return_terms) {
+    // flows: [B,2,H,W] fp32 or bf16, NCHW-contiguous. Returns the uint8
+    // masks [2B,1,H,W] (forward half, then backward half) and, on request,
+    // the fp32 residual and bound of the same shape.
+    CHECK_DEV(flow_fw); CHECK_DEV(flow_bw);
+    CHECK_CONT(flow_fw); CHECK_CONT(flow_bw);
+    TORCH_CHECK(flow_fw.dim() == 4 && flow_fw.size(1) == 2 &&
+                flow_fw.sizes() == flow_bw.sizes(),
+                "flows must both be [B,2,H,W]");
+    TORCH_CHECK(flow_fw.scalar_type() == flow_bw.scalar_type() &&
+                (flow_fw.scalar_type() == at::kFloat ||
+                 flow_fw.scalar_type() == at::kBFloat16),
+                "flows must both be fp32 or both bf16");
+    const int B = flow_fw.size(0), H = flow_fw.size(2), W = flow_fw.size(3);
+    auto occ = at::empty({2 * (int64_t)B, 1, H, W},
+                         flow_fw.options().dtype(at::kByte));
+    std::vector<at::Tensor> ret{occ};
+    float* rp = nullptr;
+    float* bp = nullptr;
+    if (return_terms) {
+        ret.push_back(at::empty({2 * (int64_t)B, 1, H, W},
+                                flow_fw.options().dtype(at::kFloat)));
+        ret.push_back(at::empty_like(ret[1]));
+        rp = ret[1].data_ptr<float>();
+        bp = ret[2].data_ptr<float>();
+    }
+    launch_fb_consistency(flow_fw.data_ptr(), flow_bw.data_ptr(),
+                          occ.data_ptr<unsigned char>(), rp, bp,
+                          flow_fw.scalar_type() == at::kBFloat16 ? 1 : 0, B,
+                          H, W, (float)alpha1, (float)alpha2,
+                          current_stream());
+    return ret;
 }
 
 at::Tensor corr_volume_nhwc_fp8(at::Tensor f1, at::Tensor f2, bool out_bf16) {
@@ -767,6 +827,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     // NHWC / fused inference path
     m.def("corr_volume_nhwc", &corr_volume_nhwc,
           "bf16 NT-GEMM correlation volume (physical NHWC fmaps)");
+    m.def("corr_volume_nhwc_bidir", &corr_volume_nhwc_bidir,
+          "forward + transposed bf16 corr volumes from one GEMM [2B,M,H,W]");
+    m.def("fb_consistency", &fb_consistency,
+          "forward-backward occlusion masks for both directions",
+          py::arg("flow_fw"), py::arg("flow_bw"), py::arg("alpha1") = 0.01,
+          py::arg("alpha2") = 0.5, py::arg("return_terms") = false);
     m.def("corr_volume_nhwc_fp8", &corr_volume_nhwc_fp8,
           "fp8 e4m3 corr volume (MX-scaled MFMA, per-tensor quant)");
     m.def("corr_volume_nhwc_fp8s", &corr_volume_nhwc_fp8s,

@@ -18,6 +18,7 @@
 
 typedef short short8 __attribute__((ext_vector_type(8)));
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
+typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
 
 #define CV_BM 128
 #define CV_BN 128
@@ -49,11 +50,16 @@ RAFT_DEV void band_remap(int super, int& mt, int& nt) {
     mt = b0 * super + rem % gh;
 }
 
-template <typename OUT_T>
-__global__ __launch_bounds__(256) void corr_volume_nhwc_bf16_k(
+// Shared tile body. BIDIR additionally writes every finished tile a second
+// time, transposed, into out_t [B, N, M] (requires M == N): the backward
+// volume C21[n, m] = C12[m, n] comes from the same fp32 accumulators with
+// the same scale and bf16 rounding, so it is the bit-exact transpose.
+template <typename OUT_T, bool BIDIR>
+RAFT_DEV void corr_volume_nhwc_tile(
     const __hip_bfloat16* __restrict__ f1,   // [B, M, K]
     const __hip_bfloat16* __restrict__ f2,   // [B, N, K]
     OUT_T* __restrict__ out,                 // [B, M, N]
+    __hip_bfloat16* __restrict__ out_t,      // [B, N, M] (BIDIR only)
     int M, int N, int K, float scale, int super) {
     __shared__ char smem[2 * CV_BM * CV_ROWB];
     char* sA = smem;
@@ -137,6 +143,7 @@ __global__ __launch_bounds__(256) void corr_volume_nhwc_bf16_k(
     // quarters HBM write efficiency — and config 4's 2.1 GB volume write
     // is the kernel's bound. Round-trip the tile through LDS (free after
     // the k-loop) and emit 16-B/lane row-contiguous stores.
+    bool fwd_done = false;
     if constexpr (std::is_same<OUT_T, __hip_bfloat16>::value) {
         if (m0 + CV_BM <= M && n0 + CV_BN <= N) {
             constexpr int STP = CV_BN + 8;    // +8 elem pad: bank rotation
@@ -159,21 +166,110 @@ __global__ __launch_bounds__(256) void corr_volume_nhwc_bf16_k(
 #pragma unroll
             for (int q = 0; q < 8; ++q)
                 *(uint4v*)(dst + q * 8) = *(const uint4v*)(src + q * 8);
-            return;
+            if constexpr (BIDIR) {
+                // Reverse store: a second LDS round trip with the tile
+                // transposed. The C fragment holds 4 consecutive m for one
+                // n, so st_t[n][m] takes one packed 8-B LDS write per
+                // fragment (16 per lane, which the compiler pairs into 8
+                // two-address writes, instead of the forward image's 64
+                // 2-B writes). Pitch: an 8-B write is banked (a/4)%32
+                // over 16-lane groups = 16 n-rows of one m-quad, so only
+                // a pitch of 2*odd dwords is conflict-free — and such rows
+                // are just 8-B aligned, which turns the read-back into
+                // half-rate two-address reads with their own 2-way
+                // conflict. The forward pitch (68 dwords, 16-B aligned
+                // rows) is 2-way on the write (rows r, r+8: 8 LDS cycles
+                // against the instruction's 6) and keeps the read-back the
+                // conflict-free ds_read_b128 of the forward path: ~160
+                // LDS cycles per wave and tile against ~230, so it stays.
+                // 16-B global stores need 16-B aligned row starts.
+                if ((M & 7) == 0) {
+                    constexpr int TP = CV_BM + 8;
+                    static_assert(CV_BN * TP * 2 <= (int)sizeof(smem),
+                                  "transposed tile must fit the k-loop LDS");
+                    __syncthreads();
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            unsigned short h[4];
+#pragma unroll
+                            for (int r = 0; r < 4; ++r)
+                                h[r] = __bfloat16_as_ushort(
+                                    (__hip_bfloat16)(acc[i][j][r] * scale));
+                            uint2v pk;
+                            pk.x = (unsigned)h[0] | ((unsigned)h[1] << 16);
+                            pk.y = (unsigned)h[2] | ((unsigned)h[3] << 16);
+                            *(uint2v*)(st + (wn + j * 16 + (lane & 15)) * TP +
+                                       wm + i * 16 + (lane >> 4) * 4) = pk;
+                        }
+                    __syncthreads();
+                    const __hip_bfloat16* srct = st + (size_t)row * TP + c0;
+                    __hip_bfloat16* dstt =
+                        out_t + ((size_t)b * N + n0 + row) * M + m0 + c0;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        *(uint4v*)(dstt + q * 8) =
+                            *(const uint4v*)(srct + q * 8);
+                    return;
+                }
+                // unaligned rows: the scalar reverse store below
+                fwd_done = true;
+            } else {
+                return;
+            }
         }
     }
+    if (!fwd_done) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
-                const int n = n0 + wn + j * 16 + (lane & 15);
-                if (m < M && n < N)
-                    out[((size_t)b * M + m) * N + n] =
-                        (OUT_T)(acc[i][j][r] * scale);
-            }
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
+                    const int n = n0 + wn + j * 16 + (lane & 15);
+                    if (m < M && n < N)
+                        out[((size_t)b * M + m) * N + n] =
+                            (OUT_T)(acc[i][j][r] * scale);
+                }
+    }
+    if constexpr (BIDIR) {
+        // edge tiles and unaligned rows: scalar guarded reverse store
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int m = m0 + wm + i * 16 + (lane >> 4) * 4 + r;
+                    const int n = n0 + wn + j * 16 + (lane & 15);
+                    if (m < M && n < N)
+                        out_t[((size_t)b * N + n) * M + m] =
+                            (__hip_bfloat16)(acc[i][j][r] * scale);
+                }
+    }
+}
+
+template <typename OUT_T>
+__global__ __launch_bounds__(256) void corr_volume_nhwc_bf16_k(
+    const __hip_bfloat16* __restrict__ f1,   // [B, M, K]
+    const __hip_bfloat16* __restrict__ f2,   // [B, N, K]
+    OUT_T* __restrict__ out,                 // [B, M, N]
+    int M, int N, int K, float scale, int super) {
+    corr_volume_nhwc_tile<OUT_T, false>(f1, f2, out, nullptr, M, N, K, scale,
+                                        super);
+}
+
+// forward volume into out, its transpose into out_t — one GEMM, two stores
+__global__ __launch_bounds__(256) void corr_volume_nhwc_bidir_k(
+    const __hip_bfloat16* __restrict__ f1,   // [B, M, K]
+    const __hip_bfloat16* __restrict__ f2,   // [B, M, K]
+    __hip_bfloat16* __restrict__ out,        // [B, M, M]
+    __hip_bfloat16* __restrict__ out_t,      // [B, M, M]
+    int M, int K, float scale, int super) {
+    corr_volume_nhwc_tile<__hip_bfloat16, true>(f1, f2, out, out_t, M, M, K,
+                                                scale, super);
 }
 
 extern "C" int corr_super_band() {
@@ -200,6 +296,18 @@ extern "C" void launch_corr_volume_nhwc_bf16(
                            0, s, (const __hip_bfloat16*)f1,
                            (const __hip_bfloat16*)f2, (float*)out,
                            M, N, K, scale, super);
+}
+
+extern "C" void launch_corr_volume_nhwc_bidir(
+    const void* f1, const void* f2, void* out, int Bsz, int M, int K,
+    float scale, hipStream_t s) {
+    // out: [2*Bsz, M, M] bf16 — forward half, then the transposed half
+    dim3 grid(cdiv(M, CV_BN), cdiv(M, CV_BM), Bsz);
+    __hip_bfloat16* o = (__hip_bfloat16*)out;
+    hipLaunchKernelGGL(corr_volume_nhwc_bidir_k, grid, dim3(256), 0, s,
+                       (const __hip_bfloat16*)f1, (const __hip_bfloat16*)f2,
+                       o, o + (size_t)Bsz * M * M, M, K, scale,
+                       corr_super_band());
 }
 
 // --------------------------------------------------------------- NHWC lookup

@@ -252,3 +252,24 @@ def convex_upsample(flow: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
 
 def upflow8(flow: torch.Tensor) -> torch.Tensor:
     return torch_ref.upflow8(flow)
+
+
+def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor,
+                   alpha1: float = 0.01, alpha2: float = 0.5):
+    """Forward-backward occlusion masks ``(occ_fw, occ_bw)``, each
+    [B,1,H,W] bool (see torch_ref.fb_consistency). On GPU one kernel
+    launch computes both directions; no autograd."""
+    if _use_hip(flow_fw):
+        from raft_amd.ops import require_hip
+        fw, bw = flow_fw.detach(), flow_bw.detach()
+        if fw.dtype != bw.dtype or fw.dtype not in (torch.float32,
+                                                    torch.bfloat16):
+            fw, bw = fw.float(), bw.float()
+        (occ,) = require_hip().fb_consistency(fw.contiguous(),
+                                              bw.contiguous(), alpha1,
+                                              alpha2, False)
+        B = fw.shape[0]
+        occ = occ.bool()
+        return occ[:B], occ[B:]
+    return (torch_ref.fb_consistency(flow_fw, flow_bw, alpha1, alpha2),
+            torch_ref.fb_consistency(flow_bw, flow_fw, alpha1, alpha2))

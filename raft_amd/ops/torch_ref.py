@@ -163,3 +163,62 @@ def upflow8(flow: torch.Tensor) -> torch.Tensor:
     B, C, H, W = flow.shape
     return F.interpolate(flow, size=(8 * H, 8 * W), mode="bilinear",
                          align_corners=True)
+
+
+def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor,
+                   alpha1: float = 0.01, alpha2: float = 0.5,
+                   return_terms: bool = False):
+    """Forward-backward consistency occlusion mask (UnFlow, Meister et al.
+    2018, with its published constants).
+
+    Per pixel (x, y) of ``flow_fw`` with f = flow_fw[:, :, y, x]:
+      p = (x, y) + f (one fp32 add per axis); ``inb`` = p inside
+      [0, W-1] x [0, H-1]; w = standard bilinear sample of ``flow_bw`` at p
+      (corners floor(p) and +1, both clamped to the frame, weights clamped
+      to [0, 1] — NOT the trunc/clamped-weight quirk of the correlation
+      lookup); res = |f + w|^2; bound = alpha1 * (|f|^2 + |w|^2) + alpha2;
+      occluded = (not inb) or res > bound.
+
+    Returns occ [B,1,H,W] bool (and res, bound [B,1,H,W] fp32 with
+    ``return_terms``). The backward mask is the same call with the
+    arguments swapped.
+    """
+    fw = flow_fw.float()
+    bw = flow_bw.float()
+    B, _, H, W = fw.shape
+    xs = torch.arange(W, device=fw.device, dtype=torch.float32)
+    ys = torch.arange(H, device=fw.device, dtype=torch.float32)
+    fx, fy = fw[:, 0], fw[:, 1]                          # [B, H, W]
+    px = xs.view(1, 1, W) + fx
+    py = ys.view(1, H, 1) + fy
+    inb = (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
+
+    # NaN -> corner 0 (the pixel is out of frame either way)
+    x0f = torch.nan_to_num(px.floor(), nan=0.0).clamp(0, W - 1)
+    y0f = torch.nan_to_num(py.floor(), nan=0.0).clamp(0, H - 1)
+    x0, y0 = x0f.long(), y0f.long()
+    x1 = (x0 + 1).clamp(max=W - 1)
+    y1 = (y0 + 1).clamp(max=H - 1)
+    ax = torch.nan_to_num(px - x0f, nan=0.0).clamp(0, 1)
+    ay = torch.nan_to_num(py - y0f, nan=0.0).clamp(0, 1)
+    w00 = (1 - ax) * (1 - ay)
+    w01 = ax * (1 - ay)
+    w10 = (1 - ax) * ay
+    w11 = ax * ay
+
+    flat = bw.reshape(B, 2, H * W)
+
+    def tap(yi, xi):
+        idx = (yi * W + xi).reshape(B, 1, H * W).expand(B, 2, H * W)
+        return flat.gather(2, idx).reshape(B, 2, H, W)
+
+    w = (w00.unsqueeze(1) * tap(y0, x0) + w01.unsqueeze(1) * tap(y0, x1)
+         + w10.unsqueeze(1) * tap(y1, x0) + w11.unsqueeze(1) * tap(y1, x1))
+    wx, wy = w[:, 0], w[:, 1]
+    sx, sy = fx + wx, fy + wy
+    res = sx * sx + sy * sy
+    bound = alpha1 * ((fx * fx + fy * fy) + (wx * wx + wy * wy)) + alpha2
+    occ = (~inb | (res > bound)).unsqueeze(1)
+    if return_terms:
+        return occ, res.unsqueeze(1), bound.unsqueeze(1)
+    return occ

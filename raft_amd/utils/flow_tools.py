@@ -72,6 +72,11 @@ def reverse_flow(flow01: np.ndarray, static_mask: Optional[np.ndarray] = None,
     static_mask: optional [H,W] bool — pixels excluded from projection
     (the reference marked them inf and skipped).
     Returns (flow10, hole_mask_before_fill).
+
+    This is an approximation from one flow field. For a real backward
+    flow and occlusion masks computed by the network in the same pass,
+    use ``InferenceEngine.bidirectional`` (``infer_raft.py
+    --bidirectional``).
     """
     h, w = flow01.shape[:2]
     f = flow01.astype(np.float64) * time_step
