@@ -35,10 +35,15 @@
 // as im2col-in-LDS MFMA GEMMs with K = taps*C (one barrier per block).
 // Every structural choice here is A/B-measured: see tools/bench_fconv.py
 // and profiles/; losers stay selectable via the RAFT_AMD_* switches
-// documented in ARCHITECTURE.md.
+// documented in ARCHITECTURE.md. Which kernel a shape gets is decided by
+// fconv_pick() in fconv_dispatch.h (plain host C++, characterised by
+// tests/test_fconv_dispatch.py); the launcher below maps that pick onto
+// the instantiations and refuses a shape that has none.
 
 #include "common.h"
+#include "fconv_dispatch.h"
 #include <hip/hip_bf16.h>
+#include <cstdio>
 
 typedef short short8 __attribute__((ext_vector_type(8)));
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
@@ -788,25 +793,92 @@ __global__ __launch_bounds__(256) void fconv_tinyn2_k(
     }
 }
 
-static inline bool tinyn2_ok(int Cin, int kh, int kw) {
-    // measured: dead even with the cell-per-wave kernel on the headline
-    // config (9.796 vs 9.799 ms/step) — the shared windows are already
-    // L2-resident there. Kept selectable (RAFT_AMD_TINYN2=1) for shapes
-    // whose windows spill L2.
-    static const int on = [] {
-        const char* e = getenv("RAFT_AMD_TINYN2");
-        return e ? atoi(e) : 0;
-    }();
-    return on && Cin % 8 == 0 && Cin <= 256 && kh <= 3 && kw <= 3;
+// ------------------------------------------------------------- dispatch
+// fconv_pick() (fconv_dispatch.h) decides which kernel a shape gets; the
+// fc_try* tables below are the one place that names the instantiations
+// of fconv_nhwc_bf16_k (78 of them) and launch the one a pick selects.
+static const FconvKnobs& fconv_knobs() {
+    static const FconvKnobs k = fconv_knobs_from_env();  // once per process
+    return k;
 }
 
-#define FCONV_ARGS                                                           \
-    (const __hip_bfloat16*)in1, C1, in1_stride, in1_off,                     \
-    (const __hip_bfloat16*)in2, C2,                                          \
-    (const __hip_bfloat16*)wp, bias, (__hip_bfloat16*)out, H, W, N, n_off,   \
-    out_cstride, act, mode, (const __hip_bfloat16*)h_state,                  \
-    (const __hip_bfloat16*)z_buf_in, (__hip_bfloat16*)z_buf_out,             \
-    (__hip_bfloat16*)rh_out
+struct FconvArgs {
+    const __hip_bfloat16 *in1, *in2, *wp;
+    const float* bias;
+    __hip_bfloat16* out;
+    const __hip_bfloat16 *h_state, *z_buf_in;
+    __hip_bfloat16 *z_buf_out, *rh_out;
+    int act;
+    hipStream_t s;
+};
+
+template <int KH, int KW, int MI, int NJ, bool AT, int MT, int S, int TH,
+          bool PIPE>
+static bool fc_try(const FconvPick& p, const FconvShape& sh,
+                   const FconvArgs& a) {
+    if (p.KH != KH || p.KW != KW || p.MI != MI || p.NJ != NJ ||
+        (p.AT != 0) != AT || p.MT != MT || p.S != S || p.TH != TH ||
+        (p.PIPE != 0) != PIPE)
+        return false;
+    unsigned g[3];
+    fconv_generic_grid(p, sh, g);
+    hipLaunchKernelGGL(
+        (fconv_nhwc_bf16_k<KH, KW, MI, NJ, AT, MT, S, TH, PIPE>),
+        dim3(g[0], g[1], g[2]), dim3(256), 0, a.s, a.in1, sh.C1,
+        sh.in1_stride, sh.in1_off, a.in2, sh.C2, a.wp, a.bias, a.out, sh.H,
+        sh.W, sh.N, sh.n_off, sh.out_cstride, a.act, sh.mode, a.h_state,
+        a.z_buf_in, a.z_buf_out, a.rh_out);
+    return true;
+}
+
+// both k-loops (single-buffered / register-prefetch) of one tile shape
+template <int KH, int KW, int MI, int NJ, bool AT, int MT, int S, int TH>
+static bool fc_try_pp(const FconvPick& p, const FconvShape& sh,
+                      const FconvArgs& a) {
+    return fc_try<KH, KW, MI, NJ, AT, MT, S, TH, false>(p, sh, a) ||
+           fc_try<KH, KW, MI, NJ, AT, MT, S, TH, true>(p, sh, a);
+}
+
+// stride-1 instantiations of one kernel shape
+template <int KH, int KW>
+static bool fc_try_s1(const FconvPick& p, const FconvShape& sh,
+                      const FconvArgs& a) {
+    if (p.S != 1 || p.KH != KH || p.KW != KW) return false;
+    // 1-row tiles: 64x128 (big); 32x32 and 32x64 (x MT m-tiles), both
+    // with and without all-taps staging, unpipelined
+    if (fc_try_pp<KH, KW, 2, 4, false, 1, 1, 1>(p, sh, a) ||
+        fc_try<KH, KW, 1, 1, false, 1, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 1, true, 1, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 2, false, 1, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 2, false, 2, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 2, false, 4, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 2, true, 1, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 2, true, 2, 1, 1, false>(p, sh, a) ||
+        fc_try<KH, KW, 1, 2, true, 4, 1, 1, false>(p, sh, a))
+        return true;
+    // 2D tiles (all-taps, TH rows): <.., NJ, AT, MT, S, TH>
+    if (fc_try_pp<KH, KW, 1, 1, true, 1, 1, 4>(p, sh, a)) return true;
+    if constexpr (KW > 1 || KH > 1) {
+        if (fc_try_pp<KH, KW, 1, 2, true, 1, 1, 4>(p, sh, a) ||
+            fc_try_pp<KH, KW, 1, 1, true, 2, 1, 4>(p, sh, a))
+            return true;
+    }
+    if constexpr (KH > 1) {
+        if (fc_try_pp<KH, KW, 1, 1, true, 1, 1, 2>(p, sh, a) ||
+            fc_try_pp<KH, KW, 1, 2, true, 1, 1, 2>(p, sh, a) ||
+            fc_try_pp<KH, KW, 1, 1, true, 1, 1, 8>(p, sh, a))
+            return true;
+    }
+    return false;
+}
+
+// stride-2 instantiations (encoder): 64x128 and 32x64, one row slab pair
+template <int K>
+static bool fc_try_s2(const FconvPick& p, const FconvShape& sh,
+                      const FconvArgs& a) {
+    return fc_try<K, K, 2, 4, false, 1, 2, 1, false>(p, sh, a) ||
+           fc_try<K, K, 1, 2, false, 1, 2, 1, false>(p, sh, a);
+}
 
 extern "C" void launch_fconv_nhwc_bf16(
     const void* in1, int C1, int in1_stride, int in1_off, const void* in2,
@@ -814,240 +886,58 @@ extern "C" void launch_fconv_nhwc_bf16(
     int W, int N, int n_off, int out_cstride, int kh, int kw, int act,
     int mode, const void* h_state, const void* z_buf_in, void* z_buf_out,
     void* rh_out, int alltaps, int mtiles, int stride, hipStream_t s) {
-    dim3 blk(256);
-    // big-tile threshold (block count of the 64x128 tiling above which the
-    // compute-efficient big tile beats small-tile grid saturation);
-    // RAFT_AMD_BIG_MIN overrides for probes.
-    static const long long big_min = [] {
-        const char* e = getenv("RAFT_AMD_BIG_MIN");
-        return e ? (long long)atoll(e) : (long long)512;
-    }();
-    const long long big_blocks0 =
-        (long long)cdiv(N, 128) * H * cdiv(W, 64) * B;
-    // N < 128 leaves half the big tile's 128 output-channel columns idle
-    // (measured: encoder N=64 3x3s run 80.7 us big vs ~55 us small even at
-    // 3520 blocks) — the big tile requires a full N extent.
-    const bool big0 = big_blocks0 >= big_min && N >= 128;
-    // alltaps (measured, tools/bench_fconv.py): wins for kh>1 on the small
-    // tile (5x1: 43.6 -> 32.8 us; 3x3 convc2: 35.5 -> 28.4), loses on the
-    // big tile (heads 3x3 N=512: 30.2 -> 39.8; LDS kills occupancy)
-    const bool at = (alltaps < 0) ? (kh > 1 && !big0) : (alltaps != 0);
-    // large tile (64x128) when it still fills the chip, else small (32x64):
-    // MI355X has 256 CUs / 8 XCDs — batch-1 grids need the small tile.
-    const long long big_blocks =
-        (long long)cdiv(N, 128) * H * cdiv(W, 64) * B;
-    const bool big = big_blocks >= big_min && N >= 128;
-    if (N <= 4 && mode == 0 && in2 == nullptr && n_off == 0 &&
-        out_cstride == N) {
+    // H, W are OUTPUT dims (stride 2: input = 2H x 2W)
+    const FconvShape sh{B, H, W, N, C1, in1_stride, in1_off, C2,
+                        in2 != nullptr, kh, kw, stride, mode, n_off,
+                        out_cstride};
+    const FconvPick p = fconv_pick(sh, alltaps, mtiles, fconv_knobs());
+    const FconvArgs a{(const __hip_bfloat16*)in1, (const __hip_bfloat16*)in2,
+                      (const __hip_bfloat16*)wp, bias, (__hip_bfloat16*)out,
+                      (const __hip_bfloat16*)h_state,
+                      (const __hip_bfloat16*)z_buf_in,
+                      (__hip_bfloat16*)z_buf_out, (__hip_bfloat16*)rh_out,
+                      act, s};
+    const dim3 blk(256);
+    switch (p.kind) {
+    case FCONV_TINYN: {
         const long long ncells = (long long)B * H * W;
-        dim3 tg((unsigned)((ncells + 3) / 4));
-        if (N == 2) {
-            if (tinyn2_ok(C1, kh, kw)) {
-                const int smem = (kh * (8 + kw - 1) * C1
-                                  + kh * kw * 2 * C1) * 2;
-                dim3 g2((unsigned)(H * ((W + 7) / 8)), 1, (unsigned)B);
-                hipLaunchKernelGGL(fconv_tinyn2_k<2>, g2, blk, smem, s,
-                                   (const __hip_bfloat16*)in1, C1,
-                                   in1_stride, in1_off,
-                                   (const __hip_bfloat16*)wp, bias,
-                                   (__hip_bfloat16*)out, nullptr, nullptr,
-                                   H, W, kh, kw, act);
-                return;
-            }
-            hipLaunchKernelGGL(fconv_tinyn_k<2>, tg, blk, 0, s,
-                               (const __hip_bfloat16*)in1, C1, in1_stride,
-                               in1_off, (const __hip_bfloat16*)wp, bias,
-                               (__hip_bfloat16*)out, nullptr, nullptr, H, W,
-                               kh, kw, act, ncells);
+        hipLaunchKernelGGL(fconv_tinyn_k<2>, dim3((unsigned)((ncells + 3) / 4)),
+                           blk, 0, s, a.in1, C1, in1_stride, in1_off, a.wp,
+                           bias, a.out, nullptr, nullptr, H, W, kh, kw, act,
+                           ncells);
+        return;
+    }
+    case FCONV_TINYN2: {
+        const int smem = (kh * (8 + kw - 1) * C1 + kh * kw * 2 * C1) * 2;
+        hipLaunchKernelGGL(fconv_tinyn2_k<2>,
+                           dim3((unsigned)(H * ((W + 7) / 8)), 1, (unsigned)B),
+                           blk, smem, s, a.in1, C1, in1_stride, in1_off, a.wp,
+                           bias, a.out, nullptr, nullptr, H, W, kh, kw, act);
+        return;
+    }
+    case FCONV_STEM:
+        hipLaunchKernelGGL(fconv_stem_s2_k,
+                           dim3(cdiv(N, 32), H * cdiv(W, 32), B), blk, 0, s,
+                           a.in1, a.wp, bias, a.out, H, W, N, act);
+        return;
+    case FCONV_GENERIC:
+        if (fc_try_s1<1, 1>(p, sh, a) || fc_try_s1<3, 3>(p, sh, a) ||
+            fc_try_s1<1, 5>(p, sh, a) || fc_try_s1<5, 1>(p, sh, a) ||
+            fc_try_s2<7>(p, sh, a) || fc_try_s2<3>(p, sh, a) ||
+            fc_try_s2<1>(p, sh, a))
             return;
-        }
+        break;
+    case FCONV_NONE:
+        break;
     }
-    // mtiles: -1 auto = 1. MT>1 was hypothesized to win by amortizing
-    // per-block weight staging but MEASURED worse nearly everywhere
-    // (tools/bench_fconv.py round14: grid saturation dominates at these
-    // batch-1 sizes) — kept selectable for larger-batch shapes.
-    // mtiles == -2: force the big (64x128) tile regardless of grid size
-    // (structure-efficiency probes).
-    const int mt = (mtiles < -1 || mtiles == 0) ? 1
-                   : (mtiles < 0 ? 1 : mtiles);
-    const bool force_big = (mtiles == -2);
-#define FC_LAUNCH(KH, KW, MI, NJ, AT, MTv, BMv, BNv)                         \
-    {                                                                        \
-        dim3 grid(cdiv(N, BNv), H * cdiv(W, (BMv) * (MTv)), B);              \
-        hipLaunchKernelGGL((fconv_nhwc_bf16_k<KH, KW, MI, NJ, AT, MTv, 1>),  \
-                           grid, blk, 0, s, FCONV_ARGS);                     \
-        return;                                                              \
-    }
-#define FC_LAUNCH2(KH, KW, MI, NJ, BMv, BNv)                                 \
-    {                                                                        \
-        dim3 grid(cdiv(N, BNv), H * cdiv(W, BMv), B);                        \
-        hipLaunchKernelGGL(                                                  \
-            (fconv_nhwc_bf16_k<KH, KW, MI, NJ, false, 1, 2>), grid, blk, 0, \
-            s, FCONV_ARGS);                                                  \
-        return;                                                              \
-    }
-    // stride-2 (encoder) shapes: H/W here are OUTPUT dims; input = 2H x 2W
-    if (stride == 2) {
-        static const int stem = [] {
-            const char* e = getenv("RAFT_AMD_STEM");
-            return e ? atoi(e) : 1;
-        }();
-        if (stem && kh == 7 && kw == 7 && C1 == 8 && C2 == 0 &&
-            mode == EP_PLAIN && n_off == 0 && out_cstride == N &&
-            in1_off == 0 && in1_stride == 8 && N <= 128) {
-            dim3 grid(cdiv(N, 32), H * cdiv(W, 32), B);
-            hipLaunchKernelGGL(fconv_stem_s2_k, grid, blk, 0, s,
-                               (const __hip_bfloat16*)in1,
-                               (const __hip_bfloat16*)wp, bias,
-                               (__hip_bfloat16*)out, H, W, N, act);
-            return;
-        }
-        const long long big2 = (long long)cdiv(N, 128) * H * cdiv(W, 64) * B;
-        const bool bigt = big2 >= big_min && N >= 128;
-        if (kh == 7 && kw == 7) {
-            if (bigt) FC_LAUNCH2(7, 7, 2, 4, 64, 128)
-            FC_LAUNCH2(7, 7, 1, 2, 32, 64)
-        }
-        if (kh == 3 && kw == 3) {
-            if (bigt) FC_LAUNCH2(3, 3, 2, 4, 64, 128)
-            FC_LAUNCH2(3, 3, 1, 2, 32, 64)
-        }
-        if (kh == 1 && kw == 1) {
-            if (bigt) FC_LAUNCH2(1, 1, 2, 4, 64, 128)
-            FC_LAUNCH2(1, 1, 1, 2, 32, 64)
-        }
-        return;  // unsupported stride-2 shape: no-op (binding checks)
-    }
-    // 32x32 tiles (2x the workgroups of 32x64) for the non-big grids:
-    // measured 12.74 -> 12.54 ms/step on the headline config — the batch-1
-    // loop shapes are latency-bound, so workgroup count beats per-wave
-    // MFMA efficiency yet again. RAFT_AMD_TILE11=0 restores 32x64.
-    static const int tile11 = [] {
-        const char* e = getenv("RAFT_AMD_TILE11");
-        return e ? atoi(e) : 1;
-    }();
-    // PIPE (register-prefetch k-loop; r2): A/B-selectable per run.
-    static const int pipe_on = [] {
-        const char* e = getenv("RAFT_AMD_PIPE");
-        return e ? atoi(e) : 1;
-    }();
-#define FC_LAUNCH_THX(KH, KW, NJ, BNv, THv)                                  \
-    {                                                                        \
-        dim3 grid(cdiv(N, BNv),                                              \
-                  ((H + THv - 1) / THv) * cdiv(W, 32 / THv), B);             \
-        /* PIPE measured: -8..-20% on 3x3/1x5/5x1 q/cv shapes, +3 us on   */ \
-        /* 1x1 (short k-loop, extra regs) — so 1x1 stays unpipelined.     */ \
-        if (pipe_on && !(KH == 1 && KW == 1))                                \
-            hipLaunchKernelGGL(                                              \
-                (fconv_nhwc_bf16_k<KH, KW, 1, NJ, true, 1, 1, THv, true>),   \
-                grid, blk, 0, s, FCONV_ARGS);                                \
-        else                                                                 \
-            hipLaunchKernelGGL(                                              \
-                (fconv_nhwc_bf16_k<KH, KW, 1, NJ, true, 1, 1, THv>), grid,   \
-                blk, 0, s, FCONV_ARGS);                                      \
-        return;                                                              \
-    }
-#define FC_LAUNCH_THX_MT2(KH, KW, THv)                                       \
-    {                                                                        \
-        dim3 grid(cdiv(N, 32),                                               \
-                  ((H + THv - 1) / THv) * cdiv(W, 2 * (32 / THv)), B);       \
-        if (pipe_on)                                                         \
-            hipLaunchKernelGGL(                                              \
-                (fconv_nhwc_bf16_k<KH, KW, 1, 1, true, 2, 1, THv, true>),    \
-                grid, blk, 0, s, FCONV_ARGS);                                \
-        else                                                                 \
-            hipLaunchKernelGGL(                                              \
-                (fconv_nhwc_bf16_k<KH, KW, 1, 1, true, 2, 1, THv>), grid,    \
-                blk, 0, s, FCONV_ARGS);                                      \
-        return;                                                              \
-    }
-    // 2D output tiles for the vertical-halo shapes (KH>1): vertical taps
-    // share staged row slabs. Measured on the headline config: TH=2
-    // 11.98 -> 11.77, TH=4 (4 rows x 8 cols) -> 10.64 ms/step; TH=4 also
-    // wins batch-8 (57.1 -> 56.6) and 1080p (37.0 -> 36.5).
-    // RAFT_AMD_TILE2D: 0 = off, 1 = TH2, 2 = TH2/BN64 (worse: LDS-limited
-    // occupancy), 4 = TH4 for KH>1, 5 = TH4 incl. 1x5 (default: 10.64 ->
-    // 10.29 ms/step — the 4-row tile wins even where it stages MORE halo,
-    // so the lever is occupancy, not just staging ratio), 8 = TH8 for 5x1
-    // (parity with TH4), 6 = MT2-under-TH4 (loses: 10.75), 7 = TH4 for
-    // every non-big shape incl. 1x1 (default: 10.33 -> 10.21 ms/step).
-    static const int tile2d = [] {
-        const char* e = getenv("RAFT_AMD_TILE2D");
-        return e ? atoi(e) : 7;
-    }();
-    // PIPE for the big (64x128) tiles too (r2): at 1080p the loop convs
-    // dispatch big and ran unpipelined at ~100 us (~13% MFMA).
-    static const int pipe_big = [] {
-        const char* e = getenv("RAFT_AMD_PIPE_BIG");
-        return e ? atoi(e) : 1;
-    }();
-#define FC_LAUNCH_BIG(KH, KW)                                                \
-    {                                                                        \
-        dim3 grid(cdiv(N, 128), H * cdiv(W, 64), B);                         \
-        if (pipe_big)                                                        \
-            hipLaunchKernelGGL(                                              \
-                (fconv_nhwc_bf16_k<KH, KW, 2, 4, false, 1, 1, 1, true>),     \
-                grid, blk, 0, s, FCONV_ARGS);                                \
-        else                                                                 \
-            hipLaunchKernelGGL(                                              \
-                (fconv_nhwc_bf16_k<KH, KW, 2, 4, false, 1, 1, 1>), grid,     \
-                blk, 0, s, FCONV_ARGS);                                      \
-        return;                                                              \
-    }
-#define FC_CASE(KH, KW)                                                      \
-    if (kh == KH && kw == KW) {                                              \
-        if (big || force_big) FC_LAUNCH_BIG(KH, KW)                          \
-        if constexpr (KH == 1 && KW == 1) {                                  \
-            /* tile2d==7 probe: 4-row tiles for 1x1 as well */               \
-            if (tile2d == 7 && !big && !force_big)                           \
-                FC_LAUNCH_THX(KH, KW, 1, 32, 4)                              \
-        }                                                                    \
-        if constexpr (KH == 1 && KW > 1) {                                   \
-            /* default (7): MT2 under TH4+PIPE — B-slice staging was the  */ \
-            /* bound for the zr shapes; whole-step 9.23 -> 8.98 ms (r2).  */ \
-            /* 9: NJ2 probe (16x32 wave tiles, 2x MFMA per barrier).      */ \
-            if (tile2d == 9 && !big && !force_big)                           \
-                FC_LAUNCH_THX(KH, KW, 2, 64, 4)                              \
-            if ((tile2d == 6 || tile2d == 7) && !big && !force_big)          \
-                FC_LAUNCH_THX_MT2(KH, KW, 4)                                 \
-            if (tile2d == 5 && !big && !force_big)                           \
-                FC_LAUNCH_THX(KH, KW, 1, 32, 4)                              \
-        }                                                                    \
-        if constexpr (KH > 1) {                                              \
-            if (tile2d && at && !big && !force_big) {                        \
-                if (tile2d == 2) FC_LAUNCH_THX(KH, KW, 2, 64, 2)             \
-                if (tile2d == 8) {                                           \
-                    if (KH == 5 && KW == 1) FC_LAUNCH_THX(KH, KW, 1, 32, 8)  \
-                    FC_LAUNCH_THX(KH, KW, 1, 32, 4)                          \
-                }                                                            \
-                if (tile2d == 9) FC_LAUNCH_THX(KH, KW, 2, 64, 4)             \
-                if (tile2d == 6 || tile2d == 7)                              \
-                    FC_LAUNCH_THX_MT2(KH, KW, 4)                             \
-                if (tile2d >= 4) FC_LAUNCH_THX(KH, KW, 1, 32, 4)             \
-                FC_LAUNCH_THX(KH, KW, 1, 32, 2)                              \
-            }                                                                \
-        }                                                                    \
-        if (tile11 && !(KH == 5 && KW == 1)) {                               \
-            /* 5x1 excluded: vertical taps share no staged rows, so the  */ \
-            /* extra workgroups just duplicate A slabs (39.1 vs 37.7 us) */ \
-            if (KH > 1 && at) FC_LAUNCH(KH, KW, 1, 1, true, 1, 32, 32)       \
-            FC_LAUNCH(KH, KW, 1, 1, false, 1, 32, 32)                        \
-        }                                                                    \
-        if (KH > 1 && at) {                                                  \
-            if (mt >= 4) FC_LAUNCH(KH, KW, 1, 2, true, 4, 32, 64)            \
-            if (mt == 2) FC_LAUNCH(KH, KW, 1, 2, true, 2, 32, 64)            \
-            FC_LAUNCH(KH, KW, 1, 2, true, 1, 32, 64)                         \
-        }                                                                    \
-        if (mt >= 4) FC_LAUNCH(KH, KW, 1, 2, false, 4, 32, 64)               \
-        if (mt == 2) FC_LAUNCH(KH, KW, 1, 2, false, 2, 32, 64)               \
-        FC_LAUNCH(KH, KW, 1, 2, false, 1, 32, 64)                            \
-    }
-    FC_CASE(1, 1)
-    FC_CASE(3, 3)
-    FC_CASE(1, 5)
-    FC_CASE(5, 1)
-#undef FC_CASE
-#undef FC_LAUNCH
+    // an unsupported shape, or a pick without an instantiation: never a
+    // silent no-op (the output buffer would stay uninitialized)
+    fprintf(stderr,
+            "fconv: no kernel for %dx%d stride %d, N=%d (pick kind %d "
+            "<%d,%d,%d,%d,%d,%d,%d,%d,%d>)\n", kh, kw, stride, N,
+            (int)p.kind, p.KH, p.KW, p.MI, p.NJ, p.AT, p.MT, p.S, p.TH,
+            p.PIPE);
+    abort();
 }
 
 // --------------------------------------------------------- small-K direct
@@ -1448,7 +1338,7 @@ extern "C" void launch_fconv_dflow_coords(
     const float* bias, const float* coords_in, float* coords_out, int B,
     int H, int W, int kh, int kw, hipStream_t s) {
     const long long ncells = (long long)B * H * W;
-    if (tinyn2_ok(Cin, kh, kw)) {
+    if (fconv_tinyn2_ok(fconv_knobs(), Cin, kh, kw)) {
         const int smem = (kh * (8 + kw - 1) * Cin + kh * kw * 2 * Cin) * 2;
         dim3 g2((unsigned)(H * ((W + 7) / 8)), 1, (unsigned)B);
         hipLaunchKernelGGL(fconv_tinyn2_k<2>, g2, dim3(256), smem, s,

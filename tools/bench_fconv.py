@@ -1,7 +1,15 @@
 """A/B microbench of the fconv variants on the raft-things @ 55x128 shapes.
 
-Within-process interleaved timing (guide §5.4 rules 9/24): N rounds per
-variant, report median us/call. Run via gpurun.
+Within-process interleaved timing: N rounds per variant, report median
+us/call. Columns aXmY pass alltaps=X, mtiles=Y to fconv_plain; `big` passes
+mtiles=-2. Which kernel each combination launches is decided by
+fconv_pick() in raft_amd/ops/csrc/fconv_dispatch.h: under the default
+RAFT_AMD_TILE2D=7 the 1x1/1x5 rows get the same 2D tile in every aXmY
+column and the kh>1 rows get it for a1; the a0 columns of the kh>1 rows
+time the 1-row tiles (3x3: 32x32, 5x1: 32x64 with Y m-tiles per block).
+Under RAFT_AMD_TILE2D=0 RAFT_AMD_TILE11=0 every column times the 1-row
+32x64 tile with Y m-tiles. The switches are read once per process: rerun
+the script per setting.
 """
 import os
 import sys
