@@ -8,7 +8,9 @@ Modes:
           directory (--warm warm-starts, --workers parallel decode) —
           and write the color-coded PNG (reference infer_raft.py:74-78;
           output file name kept); --bidirectional adds the backward flow
-          and forward-backward occlusion masks from the same pass
+          and forward-backward occlusion masks from the same pass;
+          --stream runs the directory as one video session (each frame
+          encoded once; --warm is then RAFT's projected warm start)
   train   train on synthetic pairs, or on a --data directory of flow
           triplets (Sintel dir/tree, KITTI devkit, FlyingChairs);
           preemption-safe (--resume, --save-every, SIGTERM), --accum
@@ -21,7 +23,7 @@ Modes:
 
 Flags mirror the reference (infer_raft.py:51-67): --gpu --data --load
 -m/--mode --out --batch -o/--optimizer --im1 --im2 --small, plus the
-rebuild's --iters/--size/--dtype/--steps/--warm/--bidirectional/
+rebuild's --iters/--size/--dtype/--steps/--warm/--bidirectional/--stream/
 --workers/--resume/--save-every/--accum (iters was hard-coded 20 in the
 reference, networks/RAFT.py:33).
 """
@@ -72,6 +74,14 @@ def parse_args(argv=None):
                    help="test mode: also compute the backward flow and "
                         "forward-backward occlusion masks in the same pass "
                         "(writes *_bw.flo/.png and raft_occ_*_{fw,bw}.png)")
+    p.add_argument("--stream", action="store_true",
+                   help="test mode with --data DIR: run the sorted frames "
+                        "as one video session — every frame is encoded "
+                        "once, and --warm starts each pair from the "
+                        "previous low-resolution flow projected forward "
+                        "(same output files as without the flag). Frames "
+                        "are decoded one at a time as they are pushed: "
+                        "needs --batch 1, and --workers has no effect")
     p.add_argument("--workers", type=int, default=0,
                    help="parallel decode workers for sequence/val modes")
     p.add_argument("--resume", action="store_true",
@@ -85,6 +95,8 @@ def parse_args(argv=None):
                      ("workers", 0), ("save_every", 1)):
         if getattr(args, name) < lo:
             p.error(f"--{name.replace('_', '-')} must be >= {lo}")
+    if args.stream and args.mode != "test":
+        p.error("--stream applies to --mode test with --data DIR")
     if args.iters is not None and args.iters < 1:
         p.error("--iters must be >= 1")
     return args
@@ -142,9 +154,14 @@ def mode_test(args, device):
         if not pairs:
             raise SystemExit(f"no consecutive image pairs in {args.data}")
     else:
+        if args.stream:
+            raise SystemExit("--stream needs sequence mode: pass --data "
+                             "DIR with the frames of one video (it does "
+                             "not apply to an --im1/--im2 pair)")
         pairs = [(args.im1, args.im2)]
-    ds = PairDataflow(pairs, input_size=size, batch=args.batch,
-                      workers=args.workers)
+    if args.stream and args.batch != 1:
+        raise SystemExit("--stream runs one video, frame by frame: "
+                         "use --batch 1")
     os.makedirs(args.out, exist_ok=True)
     variant = "raft-small" if args.small else "raft-things"
     prev_flow = None
@@ -160,26 +177,7 @@ def mode_test(args, device):
         return Fn.interpolate(prev, size=(h8, w8), mode="bilinear",
                               align_corners=False) / 8.0
 
-    for i, (im1, im2) in enumerate(ds):
-        flow_init = None
-        if args.warm and prev_flow is not None:
-            flow_init = _warm(prev_flow)
-            if args.bidirectional:
-                # each direction warm-starts from its own previous flow
-                flow_init = (flow_init, _warm(prev_bw))
-        t0 = time.perf_counter()
-        bidir = None
-        if args.bidirectional:
-            bidir = engine.bidirectional(im1, im2, flow_init=flow_init)
-            flow = bidir.flow_fw
-            prev_bw = bidir.flow_bw.float()
-        else:
-            flow = engine(im1, im2, flow_init=flow_init)
-        prev_flow = flow.float()
-        if device.type == "cuda":
-            torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(i, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
+    def _write(i, flow, bidir):
         # --batch > 1 decodes several pairs into one forward (the
         # reference's TODO 'check if batch_size could be free',
         # networks/RAFT.py:46) — write every sample's outputs
@@ -206,6 +204,55 @@ def mode_test(args, device):
                     write_png(f"{occ}_{tag}.png",
                               m[j, 0].cpu().numpy().astype(np.uint8) * 255)
                 print(f"wrote {stem}_bw.png and {occ}_fw.png / _bw.png")
+
+    if args.stream:
+        # one session over the sorted frames: pair i is (frame i, frame i+1)
+        from raft_amd.data.dataflow import load_image, resize_to
+        if args.workers:
+            print("--stream decodes frames as they are pushed: --workers "
+                  "ignored")
+        session = engine.stream(warm=args.warm,
+                                bidirectional=args.bidirectional)
+        for k, path in enumerate(frames):
+            img = load_image(path)
+            if size is not None:
+                img = resize_to(img, size)
+            t0 = time.perf_counter()
+            res = session.push(img.unsqueeze(0))
+            if res is None:
+                continue
+            bidir = res if args.bidirectional else None
+            flow = res.flow_fw if args.bidirectional else res
+            if device.type == "cuda":
+                torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(k - 1, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
+            _write(k - 1, flow, bidir)
+        return
+
+    ds = PairDataflow(pairs, input_size=size, batch=args.batch,
+                      workers=args.workers)
+    for i, (im1, im2) in enumerate(ds):
+        flow_init = None
+        if args.warm and prev_flow is not None:
+            flow_init = _warm(prev_flow)
+            if args.bidirectional:
+                # each direction warm-starts from its own previous flow
+                flow_init = (flow_init, _warm(prev_bw))
+        t0 = time.perf_counter()
+        bidir = None
+        if args.bidirectional:
+            bidir = engine.bidirectional(im1, im2, flow_init=flow_init)
+            flow = bidir.flow_fw
+            prev_bw = bidir.flow_bw.float()
+        else:
+            flow = engine(im1, im2, flow_init=flow_init)
+        prev_flow = flow.float()
+        if device.type == "cuda":
+            torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(i, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
+        _write(i, flow, bidir)
 
 
 def mode_val(args, device):

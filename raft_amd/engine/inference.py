@@ -149,6 +149,19 @@ class InferenceEngine:
                                             alpha1, alpha2)
         return BidirectionalFlow(fw, bw, occ_fw, occ_bw)
 
+    def stream(self, warm: bool = True, bidirectional: bool = False,
+               iters: Optional[int] = None, alpha1: float = 0.01,
+               alpha2: float = 0.5):
+        """A VideoFlowSession over this engine: push frames one at a time,
+        get the flow from the previous frame to each new one. Every frame
+        is encoded once, and ``warm`` starts each pair from the previous
+        low-resolution flow projected forward (ops.forward_project).
+        alpha1/alpha2: occlusion constants of bidirectional sessions, as
+        in ``bidirectional``."""
+        from raft_amd.engine.video import VideoFlowSession
+        return VideoFlowSession(self, warm=warm, bidirectional=bidirectional,
+                                iters=iters, alpha1=alpha1, alpha2=alpha2)
+
     def _capture(self, image1, image2, iters):
         in1 = image1.clone()
         in2 = image2.clone()

@@ -419,7 +419,8 @@ class FusedRaft:
     def _loop(self, levels, net, x_buf, coords0, coords1, iters):
         """The refinement loop + final upsample — entirely in-repo kernels,
         so it is hipGraph-capturable (BASELINE config 5) without MIOpen's
-        capture-time workspace fallbacks."""
+        capture-time workspace fallbacks. Returns (upsampled flow, the
+        1/8-resolution flow coords1 - coords0 as [B,H8,W8,2] fp32)."""
         cfg = self.model.cfg
         hip = self.hip
         B, H8, W8, _ = coords0.shape
@@ -445,55 +446,107 @@ class FusedRaft:
             up = torch_ref.upflow8(flow.permute(0, 3, 1, 2))
             if cfg.scale_small_upflow:
                 up = 8.0 * up
-            return up
+            return up, flow
         flow_nchw = flow.permute(0, 3, 1, 2).contiguous()
         mask_nchw = mask.permute(0, 3, 1, 2).contiguous()
-        return hip.convex_upsample(flow_nchw, mask_nchw)
+        return hip.convex_upsample(flow_nchw, mask_nchw), flow
 
-    @torch.no_grad()
-    def run(self, image1, image2, iters, flow_init=None,
-            bidirectional=False):
-        """bidirectional: both directions share one pass — cnet sees both
-        frames, the volume kernel stores each tile twice (forward and
-        transposed) and the loop runs at batch 2B ([fw | bw]); flow_init
-        is then already the [2B,2,H8,W8] concatenation. Returns the pair
-        (flow_fw, flow_bw)."""
-        model = self.model
-        cfg = model.cfg
-        hip = self.hip
-        img1 = model.preprocess(image1)
-        img2 = model.preprocess(image2)
-
+    def _side(self):
         side = getattr(self, "_side_stream", None)
         if side is None:
             side = torch.cuda.Stream()
             self._side_stream = side
         self.update.side_stream = side   # motion-encoder branch overlap
+        return side
+
+    @torch.no_grad()
+    def encode(self, image, want_context=True):
+        """Encoder stage for one frame batch [N,3,H,W]: preprocess,
+        8-channel NHWC staging, fnet on the current stream and
+        (``want_context``) cnet on the side stream. Returns (fmap
+        [N,H8,W8,C], context [N,H8,W8,hidden+context] or None), both
+        physical NHWC. The context is still in flight on the side stream:
+        run_pair joins it before reading. The results carry over to later
+        calls — a video session feeds each frame's maps to two consecutive
+        pairs."""
+        return self._encode([image], want_context, None)
+
+    def _encode(self, images, want_context, context_batch):
+        """encode() on several image tensors as one batch; cnet sees the
+        first ``context_batch`` rows (None: all). run() needs both: each
+        image preprocessed on its own and the context of frame 1 alone
+        keep it on the bits it has always returned."""
+        model = self.model
+        hip = self.hip
+        imgs = [model.preprocess(im) for im in images]
+        N = sum(im.shape[0] for im in imgs)
+        nc = N if context_batch is None else context_batch
+        side = self._side()
+        cur = torch.cuda.current_stream()
+        ctx = None
 
         if self.fuse_enc:
             # in-repo encoders: images -> physical NHWC padded to 8 ch
             # (Cin=3 would hit the scalar staging seam in every load)
-            B0, _, Hi, Wi = img1.shape
-            x8 = torch.zeros(2 * B0, Hi, Wi, 8, device=img1.device,
+            _, _, Hi, Wi = imgs[0].shape
+            x8 = torch.zeros(N, Hi, Wi, 8, device=imgs[0].device,
                              dtype=torch.bfloat16)
-            x8[:B0, ..., :3] = img1.permute(0, 2, 3, 1)
-            x8[B0:, ..., :3] = img2.permute(0, 2, 3, 1)
-            side.wait_stream(torch.cuda.current_stream())
+            r = 0
+            for im in imgs:
+                x8[r:r + im.shape[0], ..., :3] = im.permute(0, 2, 3, 1)
+                r += im.shape[0]
+            if want_context:
+                side.wait_stream(cur)
+                # x8 may be released before the side stream has read it
+                x8.record_stream(side)
+                with torch.cuda.stream(side):
+                    ctx = self.cnet_f(hip, x8 if nc == N
+                                      else x8[:nc].contiguous())
+            return self.fnet_f(hip, x8), ctx
+
+        x = imgs[0] if len(imgs) == 1 else torch.cat(imgs, dim=0)
+        fmaps = model.fnet(x).permute(0, 2, 3, 1).contiguous()
+        if want_context:
+            side.wait_stream(cur)
+            x.record_stream(side)
             with torch.cuda.stream(side):
-                cnet_p = self.cnet_f(hip, x8 if bidirectional
-                                     else x8[:B0].contiguous())
-            fmaps_p = self.fnet_f(hip, x8)
-            f1p = fmaps_p[:B0].contiguous()
-            f2p = fmaps_p[B0:].contiguous()
-        else:
-            fmaps = model.fnet(torch.cat([img1, img2], dim=0))
-            fmap1, fmap2 = torch.chunk(fmaps, 2, dim=0)
-            f1p = fmap1.permute(0, 2, 3, 1).contiguous()
-            f2p = fmap2.permute(0, 2, 3, 1).contiguous()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                cnet = model.cnet(torch.cat([img1, img2], dim=0)
-                                  if bidirectional else img1)
+                ctx = model.cnet(x if nc == N else x[:nc]) \
+                    .permute(0, 2, 3, 1)
+        return fmaps, ctx
+
+    @torch.no_grad()
+    def run(self, image1, image2, iters, flow_init=None,
+            bidirectional=False, return_low=False):
+        """bidirectional: both directions share one pass — cnet sees both
+        frames, the volume kernel stores each tile twice (forward and
+        transposed) and the loop runs at batch 2B ([fw | bw]); flow_init
+        is then already the [2B,2,H8,W8] concatenation. Returns the pair
+        (flow_fw, flow_bw). return_low appends the 1/8-resolution flow(s),
+        see run_pair."""
+        B0 = image1.shape[0]
+        fmaps, ctx = self._encode([image1, image2], True,
+                                  None if bidirectional else B0)
+        return self.run_pair(fmaps[:B0].contiguous(),
+                             fmaps[B0:].contiguous(), ctx, None, iters,
+                             flow_init, bidirectional, return_low)
+
+    @torch.no_grad()
+    def run_pair(self, f1p, f2p, ctx1, ctx2=None, iters=None,
+                 flow_init=None, bidirectional=False, return_low=False):
+        """Pair stage: everything from the correlation volume on, fed with
+        encode() results. f1p/f2p: [B,H8,W8,C] feature maps of the two
+        frames; ctx1: context of frame 1 — bidirectional runs also need
+        frame 2's, either as ctx2 or already stacked under ctx1 ([2B]
+        rows, frame 1 first). Returns the upsampled flow, or (flow_fw,
+        flow_bw); with return_low followed by the 1/8-resolution flow
+        [B,2,H8,W8] fp32 (one per direction) — the quantity flow_init
+        seeds. Under graph replay the results live in static buffers that
+        the next replay of the same shape overwrites: clone to keep."""
+        model = self.model
+        cfg = model.cfg
+        hip = self.hip
+        side = self._side()
+        iters = iters if iters is not None else cfg.iters
         B, H8, W8, C = f1p.shape
 
         import os as _os
@@ -536,17 +589,20 @@ class FusedRaft:
             else:
                 levels.append(pool(last))
 
+        # join the context encoder(s): every cnet launched so far sits on
+        # the side stream, a cached one from an earlier call included
         torch.cuda.current_stream().wait_stream(side)
-        if self.fuse_enc:
-            cnet_p.record_stream(torch.cuda.current_stream())
-            net = torch.tanh(cnet_p[..., :cfg.hidden_dim]).contiguous()
-            inp = torch.relu(cnet_p[..., cfg.hidden_dim:]).contiguous()
-        else:
-            cnet.record_stream(torch.cuda.current_stream())
-            net, inp = torch.split(cnet, [cfg.hidden_dim, cfg.context_dim],
-                                   dim=1)
-            net = torch.tanh(net).permute(0, 2, 3, 1).contiguous()
-            inp = torch.relu(inp).permute(0, 2, 3, 1).contiguous()
+        for c in (ctx1, ctx2):
+            if c is not None:
+                c.record_stream(torch.cuda.current_stream())
+        ctx = ctx1 if ctx2 is None else torch.cat([ctx1, ctx2], dim=0)
+        if ctx.shape[0] != B:
+            raise ValueError(f"context has {ctx.shape[0]} rows, the loop "
+                             f"batch is {B}" + (" (bidirectional runs need "
+                                                "both frames' context)"
+                                                if bidirectional else ""))
+        net = torch.tanh(ctx[..., :cfg.hidden_dim]).contiguous()
+        inp = torch.relu(ctx[..., cfg.hidden_dim:]).contiguous()
 
         ys, xs = torch.meshgrid(
             torch.arange(H8, device=net.device, dtype=torch.float32),
@@ -571,8 +627,9 @@ class FusedRaft:
             x_buf = torch.empty(B, H8, W8, self.x_dim, device=net.device,
                                 dtype=torch.bfloat16)
             x_buf[..., :cfg.context_dim] = inp
-            out = self._loop(levels, net, x_buf, coords0, coords1, iters)
-            return (out[:B // 2], out[B // 2:]) if bidirectional else out
+            out, low = self._loop(levels, net, x_buf, coords0, coords1,
+                                  iters)
+            return self._result(out, low, bidirectional, return_low)
 
         # a bidirectional run shares the captured loop of a unidirectional
         # batch-2B run (identical kernels) — except under RAFT_AMD_FP8_CORR,
@@ -586,10 +643,9 @@ class FusedRaft:
                 x_buf = torch.empty(B, H8, W8, self.x_dim,
                                     device=net.device, dtype=torch.bfloat16)
                 x_buf[..., :cfg.context_dim] = inp
-                out = self._loop(levels, net, x_buf, coords0, coords1,
-                                 iters)
-                return (out[:B // 2], out[B // 2:]) if bidirectional \
-                    else out
+                out, low = self._loop(levels, net, x_buf, coords0, coords1,
+                                      iters)
+                return self._result(out, low, bidirectional, return_low)
             entry = self._capture(levels, net, inp, coords0, coords1, iters)
             self._graphs[key] = entry
         graph, st = entry
@@ -601,8 +657,18 @@ class FusedRaft:
         if st.get("vol_scale") is not None:   # fp8-storage dequant scalar
             st["vol_scale"].copy_(self._vol_scale)
         graph.replay()
-        out = st["out"]
-        return (out[:B // 2], out[B // 2:]) if bidirectional else out
+        return self._result(st["out"], st["low"], bidirectional, return_low)
+
+    @staticmethod
+    def _result(out, low, bidirectional, return_low):
+        """Shape run_pair's return value: out [B,2,H,W], low the loop's
+        [B,H8,W8,2] flow (returned as its logical [B,2,H8,W8] view)."""
+        h = out.shape[0] // 2
+        res = (out[:h], out[h:]) if bidirectional else (out,)
+        if return_low:
+            low = low.permute(0, 3, 1, 2)
+            res += (low[:h], low[h:]) if bidirectional else (low,)
+        return res if len(res) > 1 else res[0]
 
     def _capture(self, levels, net, inp, coords0, coords1, iters):
         cfg = self.model.cfg
@@ -632,8 +698,9 @@ class FusedRaft:
         torch.cuda.current_stream().wait_stream(s)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            st["out"] = self._loop(st["levels"], st["net"], st["x_buf"],
-                                   st["coords0"], st["coords1"], iters)
+            st["out"], st["low"] = self._loop(
+                st["levels"], st["net"], st["x_buf"], st["coords0"],
+                st["coords1"], iters)
         return graph, st
 
 

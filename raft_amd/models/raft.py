@@ -97,7 +97,8 @@ class RAFT(nn.Module):
     # ------------------------------------------------------------------
     def forward(self, image1: torch.Tensor, image2: torch.Tensor,
                 iters: Optional[int] = None, flow_init: Optional[torch.Tensor] = None,
-                test_mode: bool = True, bidirectional: bool = False):
+                test_mode: bool = True, bidirectional: bool = False,
+                return_low: bool = False):
         """Run the recurrent refinement.
 
         image1/image2: [B, 3, H, W] BGR in [0,1] (H, W divisible by 8 —
@@ -112,10 +113,18 @@ class RAFT(nn.Module):
         already sees both frames, the backward correlation volume is the
         transpose of the forward one, and the loop runs both directions
         as one batch of 2B. flow_init is then None or ``(init_fw, init_bw)``.
+
+        return_low=True (test_mode only) also returns the final
+        1/8-resolution flow [B,2,H/8,W/8] fp32 — the quantity flow_init
+        seeds, so a video session can project it into the next pair's
+        warm start: ``(up, low)``, or ``(fw, bw, low_fw, low_bw)`` when
+        bidirectional.
         """
         iters = iters if iters is not None else self.cfg.iters
         if iters < 1:
             raise ValueError(f"iters must be >= 1, got {iters}")
+        if return_low and not test_mode:
+            raise ValueError("return_low=True needs test_mode=True")
         if bidirectional:
             if not test_mode:
                 raise ValueError("bidirectional=True needs test_mode=True "
@@ -133,7 +142,8 @@ class RAFT(nn.Module):
             from raft_amd.models import fused
             if fused.can_fuse(self, image1):
                 return fused.get_fused(self).run(image1, image2, iters,
-                                                 flow_init, bidirectional)
+                                                 flow_init, bidirectional,
+                                                 return_low)
 
         img1 = self.preprocess(image1)
         img2 = self.preprocess(image2)
@@ -184,11 +194,14 @@ class RAFT(nn.Module):
 
         if not test_mode:
             return flow_predictions
-        up = self._upsample(coords1 - coords0, up_mask)
+        low = coords1 - coords0
+        up = self._upsample(low, up_mask)
         if bidirectional:
             B = image1.shape[0]
+            if return_low:
+                return up[:B], up[B:], low[:B], low[B:]
             return up[:B], up[B:]
-        return up
+        return (up, low) if return_low else up
 
     def _upsample(self, flow: torch.Tensor, up_mask: Optional[torch.Tensor]):
         if self.cfg.small:

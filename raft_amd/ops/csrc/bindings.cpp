@@ -68,6 +68,8 @@ void launch_corr_volume_nhwc_bidir(const void*, const void*, void*, int, int,
 void launch_fb_consistency(const void*, const void*, unsigned char*, float*,
                            float*, int, int, int, int, float, float,
                            hipStream_t);
+int launch_flow_project(const float*, unsigned long long*, float*,
+                        unsigned char*, int, int, int, int, hipStream_t);
 void launch_corr_lookup_nhwc(const void* const*, const int*, const int*,
                              int, const float*, const float*, void*, bool,
                              void*, int, int, int, int, int, int, int, int,
@@ -437,6 +439,33 @@ std::vector<at::Tensor> fb_consistency(at::Tensor flow_fw, at::Tensor flow_bw,
                           H, W, (float)alpha1, (float)alpha2,
                           current_stream());
     return ret;
+}
+
+std::vector<at::Tensor> forward_project(at::Tensor flow, int64_t direction) {
+    // flow: [B,2,H,W] fp32 NCHW-contiguous. Returns (projected [B,2,H,W]
+    // fp32, holes [B,1,H,W] bool). Memset + two kernels on the current
+    // stream; the key scratch buffer comes from the caching allocator, so
+    // the call is capturable.
+    CHECK_DEV(flow); CHECK_CONT(flow);
+    TORCH_CHECK(flow.dim() == 4 && flow.size(1) == 2,
+                "flow must be [B,2,H,W]");
+    TORCH_CHECK(flow.scalar_type() == at::kFloat, "flow must be fp32");
+    TORCH_CHECK(direction == 1 || direction == -1,
+                "direction must be +1 or -1");
+    const int64_t B = flow.size(0), H = flow.size(2), W = flow.size(3);
+    // the source index shares a 64-bit key with the distance bits
+    TORCH_CHECK(H * W < (int64_t(1) << 31), "H*W must be below 2^31");
+    auto out = at::empty_like(flow);
+    auto holes = at::empty({B, 1, H, W}, flow.options().dtype(at::kBool));
+    if (flow.numel() == 0) return {out, holes};
+    auto keys = at::empty({B, H, W}, flow.options().dtype(at::kLong));
+    const int err = launch_flow_project(
+        flow.data_ptr<float>(), (unsigned long long*)keys.data_ptr<int64_t>(),
+        out.data_ptr<float>(), (unsigned char*)holes.data_ptr<bool>(), (int)B,
+        (int)H, (int)W, (int)direction, current_stream());
+    TORCH_CHECK(err == 0, "forward_project: ",
+                hipGetErrorString((hipError_t)err));
+    return {out, holes};
 }
 
 at::Tensor corr_volume_nhwc_fp8(at::Tensor f1, at::Tensor f2, bool out_bf16) {
@@ -833,6 +862,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "forward-backward occlusion masks for both directions",
           py::arg("flow_fw"), py::arg("flow_bw"), py::arg("alpha1") = 0.01,
           py::arg("alpha2") = 0.5, py::arg("return_terms") = false);
+    m.def("forward_project", &forward_project,
+          "deterministic forward projection of a flow field -> "
+          "(projected, holes)",
+          py::arg("flow"), py::arg("direction") = 1);
     m.def("corr_volume_nhwc_fp8", &corr_volume_nhwc_fp8,
           "fp8 e4m3 corr volume (MX-scaled MFMA, per-tensor quant)");
     m.def("corr_volume_nhwc_fp8s", &corr_volume_nhwc_fp8s,

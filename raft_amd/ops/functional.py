@@ -273,3 +273,25 @@ def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor,
         return occ[:B], occ[B:]
     return (torch_ref.fb_consistency(flow_fw, flow_bw, alpha1, alpha2),
             torch_ref.fb_consistency(flow_bw, flow_fw, alpha1, alpha2))
+
+
+def forward_project(flow: torch.Tensor, direction: int = 1):
+    """Forward projection of a flow field along itself (``direction=+1``)
+    or against itself (``-1``): ``(projected [B,2,H,W] fp32, holes
+    [B,1,H,W] bool)``. See torch_ref.forward_project for the definition;
+    the GPU kernels match it bit for bit, are stream-ordered (no host
+    sync) and graph-capturable. No autograd. As with every op here, a
+    CUDA tensor without the built extension is an error, not a fall-back
+    to the oracle; ``RAFT_AMD_FORCE_TORCH=1`` selects the oracle
+    explicitly."""
+    if direction not in (1, -1):
+        raise ValueError(f"direction must be +1 or -1, got {direction}")
+    if _use_hip(flow):
+        from raft_amd.ops import require_hip
+        if flow.dim() != 4 or flow.shape[1] != 2:
+            raise ValueError(f"flow must be [B,2,H,W], got "
+                             f"{tuple(flow.shape)}")
+        out, holes = require_hip().forward_project(
+            flow.detach().float().contiguous(), direction)
+        return out, holes
+    return torch_ref.forward_project(flow.detach(), direction)

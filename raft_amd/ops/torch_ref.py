@@ -222,3 +222,110 @@ def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor,
     if return_terms:
         return occ, res.unsqueeze(1), bound.unsqueeze(1)
     return occ
+
+
+def forward_project(flow: torch.Tensor, direction: int = 1):
+    """Deterministic forward projection of a flow field — RAFT's warm start
+    (``forward_interpolate``) as a nearest-source splat. This definition is
+    the contract: the HIP kernel (csrc/flow_project.hip) matches it bit for
+    bit.
+
+    flow: [B,2,H,W] fp32. Returns (projected [B,2,H,W] fp32, holes
+    [B,1,H,W] bool, taken before filling).
+
+    Scatter: source cell (x, y), linear index i = y*W + x, value f, targets
+    t = (x + fx, y + fy) for ``direction=+1`` and (x - fx, y - fy) for
+    ``direction=-1`` (one fp32 add / subtract per coordinate). It is valid
+    iff 0 <= tx <= W-1 and 0 <= ty <= H-1 (NaN / Inf are dropped) and is
+    then a candidate for the in-grid cells of {floor(tx), floor(tx)+1} x
+    {floor(ty), floor(ty)+1} at distance d2 = dx*dx + dy*dy (products and
+    sum rounded separately, no FMA).
+    Winner: each cell takes the value f (never negated) of the candidate
+    with the smallest d2, exact ties to the lowest i — the minimum of the
+    64-bit key (float_bits(d2) << 32) | i, independent of execution order.
+    Holes: a cell without candidate takes the mean of the nearest covered
+    cells to its left, right, above and below — added in that order from
+    0.0, divided by their count (correctly rounded) — or 0 when its row
+    and column hold none (utils.flow_tools._fill_holes_nearest4).
+
+    ``direction=+1`` is the constant-velocity warm start of the forward
+    flow; ``direction=-1`` the same assumption for the backward flow of
+    the next pair (a point at x in frame t+1 with backward flow b sits at
+    x - b in frame t+2 and keeps b).
+    """
+    if direction not in (1, -1):
+        raise ValueError(f"direction must be +1 or -1, got {direction}")
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError(f"flow must be [B,2,H,W], got {tuple(flow.shape)}")
+    f = flow.float().contiguous()
+    B, _, H, W = f.shape
+    dev = f.device
+    HW = H * W
+    if B * HW == 0:
+        return f.clone(), torch.zeros(B, 1, H, W, dtype=torch.bool,
+                                      device=dev)
+    xs = torch.arange(W, device=dev, dtype=torch.float32).view(1, 1, W)
+    ys = torch.arange(H, device=dev, dtype=torch.float32).view(1, H, 1)
+    fx, fy = f[:, 0], f[:, 1]                            # [B, H, W]
+    tx = xs + fx if direction > 0 else xs - fx
+    ty = ys + fy if direction > 0 else ys - fy
+    valid = (tx >= 0) & (tx <= W - 1) & (ty >= 0) & (ty <= H - 1)
+    x0 = torch.where(valid, tx, torch.zeros_like(tx)).floor()
+    y0 = torch.where(valid, ty, torch.zeros_like(ty)).floor()
+
+    empty = torch.iinfo(torch.int64).max
+    keys = torch.full((B * HW,), empty, dtype=torch.int64, device=dev)
+    src = torch.arange(HW, device=dev, dtype=torch.int64).view(1, H, W)
+    base = (torch.arange(B, device=dev, dtype=torch.int64) * HW) \
+        .view(B, 1, 1)
+    for dy in (0.0, 1.0):
+        for dx in (0.0, 1.0):
+            qx, qy = x0 + dx, y0 + dy
+            ok = valid & (qx <= W - 1) & (qy <= H - 1)
+            ddx, ddy = tx - qx, ty - qy
+            d2 = (ddx * ddx + ddy * ddy).contiguous()
+            key = (d2.view(torch.int32).to(torch.int64) << 32) | src
+            cell = base + (qy * W + qx).long()
+            keys.scatter_reduce_(0, cell[ok], key[ok], reduce="amin")
+
+    cov = (keys != empty).view(B, H, W)
+    winner = (keys & 0xFFFFFFFF).view(B, 1, HW).expand(B, 2, HW)
+    winner = torch.where(cov.view(B, 1, HW), winner,
+                         torch.zeros_like(winner))
+    val = f.view(B, 2, HW).gather(2, winner).view(B, 2, H, W)
+    val = torch.where(cov.unsqueeze(1), val, torch.zeros_like(val))
+
+    def nearest(dim: int, reverse: bool):
+        """Value and presence of the nearest covered cell strictly before
+        (or after, ``reverse``) each cell along ``dim`` of [B,H,W]."""
+        n = cov.shape[dim]
+        c, v = cov, val
+        if reverse:
+            c, v = c.flip(dim), v.flip(dim + 1)
+        shape = [1, 1, 1]
+        shape[dim] = n
+        pos = torch.arange(n, device=dev).view(shape)
+        last = torch.where(c, pos, torch.full_like(pos, -1)) \
+            .cummax(dim).values
+        # strictly before: shift by one along dim
+        last = torch.cat([torch.full_like(last.narrow(dim, 0, 1), -1),
+                          last.narrow(dim, 0, n - 1)], dim=dim)
+        has = last >= 0
+        idx = last.clamp(min=0).unsqueeze(1).expand(B, 2, H, W)
+        got = v.gather(dim + 1, idx)
+        if reverse:
+            has, got = has.flip(dim), got.flip(dim + 1)
+        return got, has
+
+    total = torch.zeros_like(val)
+    count = torch.zeros(B, H, W, dtype=torch.float32, device=dev)
+    for dim, reverse in ((2, False), (2, True), (1, False), (1, True)):
+        got, has = nearest(dim, reverse)
+        total = total + torch.where(has.unsqueeze(1), got,
+                                    torch.zeros_like(got))
+        count = count + has.float()
+    fill = torch.where((count > 0).unsqueeze(1),
+                       total / count.clamp(min=1.0).unsqueeze(1),
+                       torch.zeros_like(total))
+    out = torch.where(cov.unsqueeze(1), val, fill)
+    return out, ~cov.unsqueeze(1)

@@ -76,7 +76,10 @@ def reverse_flow(flow01: np.ndarray, static_mask: Optional[np.ndarray] = None,
     This is an approximation from one flow field. For a real backward
     flow and occlusion masks computed by the network in the same pass,
     use ``InferenceEngine.bidirectional`` (``infer_raft.py
-    --bidirectional``).
+    --bidirectional``). For projecting a flow forward along itself on the
+    device (RAFT's warm start; nearest source instead of conflict
+    averaging, the same four-direction hole fill) use
+    ``raft_amd.ops.forward_project``.
     """
     h, w = flow01.shape[:2]
     f = flow01.astype(np.float64) * time_step
