@@ -10,7 +10,9 @@ Modes:
           output file name kept); --bidirectional adds the backward flow
           and forward-backward occlusion masks from the same pass;
           --stream runs the directory as one video session (each frame
-          encoded once; --warm is then RAFT's projected warm start)
+          encoded once; --warm is then RAFT's projected warm start);
+          --interp N (implies --bidirectional) also writes N evenly
+          spaced in-between frames of every pair
   train   train on synthetic pairs, or on a --data directory of flow
           triplets (Sintel dir/tree, KITTI devkit, FlyingChairs);
           preemption-safe (--resume, --save-every, SIGTERM), --accum
@@ -24,8 +26,8 @@ Modes:
 Flags mirror the reference (infer_raft.py:51-67): --gpu --data --load
 -m/--mode --out --batch -o/--optimizer --im1 --im2 --small, plus the
 rebuild's --iters/--size/--dtype/--steps/--warm/--bidirectional/--stream/
---workers/--resume/--save-every/--accum (iters was hard-coded 20 in the
-reference, networks/RAFT.py:33).
+--interp/--workers/--resume/--save-every/--accum (iters was hard-coded 20
+in the reference, networks/RAFT.py:33).
 """
 import argparse
 import json
@@ -82,6 +84,12 @@ def parse_args(argv=None):
                         "(same output files as without the flag). Frames "
                         "are decoded one at a time as they are pushed: "
                         "needs --batch 1, and --workers has no effect")
+    p.add_argument("--interp", type=int, default=0, metavar="N",
+                   help="test mode: also write N evenly spaced in-between "
+                        "frames of every pair (t = k/(N+1)) as "
+                        "raft_interp_*_tK.png next to the flow output; "
+                        "implies --bidirectional; with --stream they come "
+                        "from the session (between)")
     p.add_argument("--workers", type=int, default=0,
                    help="parallel decode workers for sequence/val modes")
     p.add_argument("--resume", action="store_true",
@@ -92,13 +100,17 @@ def parse_args(argv=None):
                    help="micro-batches accumulated per optimizer step")
     args = p.parse_args(argv)
     for name, lo in (("batch", 1), ("steps", 1), ("accum", 1),
-                     ("workers", 0), ("save_every", 1)):
+                     ("workers", 0), ("save_every", 1), ("interp", 0)):
         if getattr(args, name) < lo:
             p.error(f"--{name.replace('_', '-')} must be >= {lo}")
     if args.stream and args.mode != "test":
         p.error("--stream applies to --mode test with --data DIR")
     if args.iters is not None and args.iters < 1:
         p.error("--iters must be >= 1")
+    if args.interp:
+        if args.mode != "test":
+            p.error("--interp applies to --mode test")
+        args.bidirectional = True
     return args
 
 
@@ -205,6 +217,22 @@ def mode_test(args, device):
                               m[j, 0].cpu().numpy().astype(np.uint8) * 255)
                 print(f"wrote {stem}_bw.png and {occ}_fw.png / _bw.png")
 
+    times = [k / (args.interp + 1) for k in range(1, args.interp + 1)]
+
+    def _write_interp(i, frames_t):
+        # frames_t: [T,B,3,H,W] fp32 in the inputs' [0,1] BGR range
+        u8 = (frames_t.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8) \
+            .permute(0, 1, 3, 4, 2).cpu().numpy()
+        for j in range(u8.shape[1]):
+            idx = i * args.batch + j
+            suffix = f"_{idx:04d}" if len(pairs) > 1 else ""
+            for k in range(u8.shape[0]):
+                path = os.path.join(
+                    args.out, f"raft_interp_{variant}{suffix}_t{k + 1}.png")
+                write_png(path, np.ascontiguousarray(u8[k, j]))
+            print(f"wrote {u8.shape[0]} in-between frame(s) "
+                  f"raft_interp_{variant}{suffix}_t*.png")
+
     if args.stream:
         # one session over the sorted frames: pair i is (frame i, frame i+1)
         from raft_amd.data.dataflow import load_image, resize_to
@@ -228,6 +256,8 @@ def mode_test(args, device):
             dt = time.perf_counter() - t0
             print(k - 1, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
             _write(k - 1, flow, bidir)
+            if times:
+                _write_interp(k - 1, session.between(times))
         return
 
     ds = PairDataflow(pairs, input_size=size, batch=args.batch,
@@ -253,6 +283,11 @@ def mode_test(args, device):
         dt = time.perf_counter() - t0
         print(i, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
         _write(i, flow, bidir)
+        if times:
+            from raft_amd.engine.inference import interpolate_between
+            _write_interp(i, interpolate_between(
+                im1.to(engine.device, engine.dtype),
+                im2.to(engine.device, engine.dtype), bidir, times))
 
 
 def mode_val(args, device):

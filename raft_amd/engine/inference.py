@@ -41,6 +41,31 @@ class BidirectionalFlow(NamedTuple):
     occ_bw: torch.Tensor
 
 
+def _check_times(times) -> Tuple[float, ...]:
+    times = tuple(float(t) for t in times)
+    for t in times:
+        if not 0.0 <= t <= 1.0:
+            raise ValueError(f"interpolation times must lie in [0, 1], "
+                             f"got {t}")
+    return times
+
+
+def interpolate_between(image1: torch.Tensor, image2: torch.Tensor,
+                        bidir: BidirectionalFlow, times) -> torch.Tensor:
+    """In-between frames [T,B,C,H,W] fp32 of two unpadded frames from
+    their BidirectionalFlow: one ops.interpolate_frame call per time."""
+    from raft_amd import ops
+    times = _check_times(times)
+    fw = bidir.flow_fw.float().contiguous()
+    bw = bidir.flow_bw.float().contiguous()
+    frames = [ops.interpolate_frame(image1, image2, fw, bw, bidir.occ_fw,
+                                    bidir.occ_bw, t)[0] for t in times]
+    if not frames:
+        return image1.new_zeros((0,) + tuple(image1.shape),
+                                dtype=torch.float32)
+    return torch.stack(frames, dim=0)
+
+
 class InferenceEngine:
     """Wraps a RAFT model for serving-style inference.
 
@@ -148,6 +173,24 @@ class InferenceEngine:
         occ_fw, occ_bw = ops.fb_consistency(fw.contiguous(), bw.contiguous(),
                                             alpha1, alpha2)
         return BidirectionalFlow(fw, bw, occ_fw, occ_bw)
+
+    @torch.no_grad()
+    def interpolate(self, image1: torch.Tensor, image2: torch.Tensor,
+                    times=(0.5,), iters: Optional[int] = None,
+                    alpha1: float = 0.01, alpha2: float = 0.5
+                    ) -> torch.Tensor:
+        """Frames between ``image1`` (t=0) and ``image2`` (t=1) at the
+        given times in [0, 1]: one ``bidirectional`` pass, then one
+        ops.interpolate_frame call per time. Returns [T,B,C,H,W] fp32 in
+        the value range of the inputs (as the engine's dtype holds them).
+        The op runs on the unpadded images and flows, so "inside the
+        frame" means the real frame, not the pad8 canvas."""
+        times = _check_times(times)
+        image1 = image1.to(self.device, self.dtype, non_blocking=True)
+        image2 = image2.to(self.device, self.dtype, non_blocking=True)
+        bidir = self.bidirectional(image1, image2, iters=iters,
+                                   alpha1=alpha1, alpha2=alpha2)
+        return interpolate_between(image1, image2, bidir, times)
 
     def stream(self, warm: bool = True, bidirectional: bool = False,
                iters: Optional[int] = None, alpha1: float = 0.01,

@@ -19,7 +19,8 @@ from typing import Optional
 
 import torch
 
-from raft_amd.engine.inference import BidirectionalFlow, pad8, unpad
+from raft_amd.engine.inference import (BidirectionalFlow,
+                                       interpolate_between, pad8, unpad)
 
 
 class VideoFlowSession:
@@ -29,6 +30,9 @@ class VideoFlowSession:
     the previous frame to the pushed one, unpadded, [B,2,H,W] — a
     BidirectionalFlow (flows + occlusion masks) for bidirectional
     sessions. Returned tensors stay valid after later pushes.
+
+    ``between(times)`` of a bidirectional session returns the in-between
+    frames of the last two pushed frames (ops.interpolate_frame).
     """
 
     def __init__(self, engine, warm: bool = True,
@@ -49,6 +53,8 @@ class VideoFlowSession:
         self._prev = None       # fused: (fmap, context); fallback: frame
         self.last_low = None    # previous pair's 1/8 flow (fw) — warm seed
         self.last_low_bw = None
+        self._frames = (None, None)   # last two unpadded frames (references)
+        self._last_bidir = None       # their BidirectionalFlow
 
     # ------------------------------------------------------------------
     def _flow_init(self):
@@ -69,6 +75,7 @@ class VideoFlowSession:
         eng = self.engine
         model = eng.model
         frame = frame.to(eng.device, eng.dtype, non_blocking=True)
+        raw = frame
         frame, hw = pad8(frame)
         if eng.device.type == "cuda":
             frame = frame.contiguous(memory_format=torch.channels_last)
@@ -109,6 +116,7 @@ class VideoFlowSession:
                 self._prev, frame, iters=iters, flow_init=init,
                 bidirectional=bidir, return_low=True)
         self._prev, self._runner, self._shape = cur, runner, shape
+        self._frames = (self._frames[1], raw)
         if res is None:
             return None
 
@@ -125,4 +133,22 @@ class VideoFlowSession:
         # on the unpadded (contiguous) flows, as engine.bidirectional does
         occ_fw, occ_bw = ops.fb_consistency(flows[0], flows[1], self.alpha1,
                                             self.alpha2)
-        return BidirectionalFlow(flows[0], flows[1], occ_fw, occ_bw)
+        self._last_bidir = BidirectionalFlow(flows[0], flows[1], occ_fw,
+                                             occ_bw)
+        return self._last_bidir
+
+    @torch.no_grad()
+    def between(self, times=(0.5,)) -> torch.Tensor:
+        """Frames [T,B,C,H,W] fp32 between the last two pushed frames at
+        the given times in [0, 1] (0 = the older frame), from the flows
+        and masks the last push returned."""
+        if not self.bidirectional:
+            raise ValueError(
+                "between() needs a bidirectional session (backward flow "
+                "and occlusion masks): build it with "
+                "stream(bidirectional=True)")
+        if self._last_bidir is None:
+            raise RuntimeError("between() needs two pushed frames: push a "
+                               "second frame first")
+        return interpolate_between(self._frames[0], self._frames[1],
+                                   self._last_bidir, times)

@@ -70,6 +70,11 @@ void launch_fb_consistency(const void*, const void*, unsigned char*, float*,
                            hipStream_t);
 int launch_flow_project(const float*, unsigned long long*, float*,
                         unsigned char*, int, int, int, int, hipStream_t);
+int launch_frame_interp(const float*, const float*, const float*,
+                        const float*, const unsigned char*,
+                        const unsigned char*, unsigned long long*, float*,
+                        float*, float*, unsigned char*, int, int, int, int,
+                        float, hipStream_t);
 void launch_corr_lookup_nhwc(const void* const*, const int*, const int*,
                              int, const float*, const float*, void*, bool,
                              void*, int, int, int, int, int, int, int, int,
@@ -466,6 +471,66 @@ std::vector<at::Tensor> forward_project(at::Tensor flow, int64_t direction) {
     TORCH_CHECK(err == 0, "forward_project: ",
                 hipGetErrorString((hipError_t)err));
     return {out, holes};
+}
+
+std::vector<at::Tensor> interpolate_frame(at::Tensor im0, at::Tensor im1,
+                                          at::Tensor fw, at::Tensor bw,
+                                          at::Tensor occ_fw,
+                                          at::Tensor occ_bw, double t) {
+    // im0/im1: [B,C,H,W] fp32; fw/bw: [B,2,H,W] fp32; occ_*: [B,1,H,W]
+    // uint8 (non-zero = occluded); all NCHW-contiguous on one device.
+    // Returns (frame [B,C,H,W] fp32, flow_t0, flow_t1 [B,2,H,W] fp32,
+    // cover [B,1,H,W] uint8: bit 0 splat A, bit 1 splat B). Memset + two
+    // kernels on the current stream; the key scratch buffer comes from the
+    // caching allocator, so the call is capturable.
+    CHECK_DEV(im0); CHECK_DEV(im1); CHECK_DEV(fw); CHECK_DEV(bw);
+    CHECK_DEV(occ_fw); CHECK_DEV(occ_bw);
+    CHECK_CONT(im0); CHECK_CONT(im1); CHECK_CONT(fw); CHECK_CONT(bw);
+    CHECK_CONT(occ_fw); CHECK_CONT(occ_bw);
+    TORCH_CHECK(im0.dim() == 4 && im0.size(1) >= 1 &&
+                im0.sizes() == im1.sizes(),
+                "images must both be [B,C,H,W] with C >= 1");
+    const int64_t B = im0.size(0), C = im0.size(1), H = im0.size(2),
+                  W = im0.size(3);
+    TORCH_CHECK(fw.dim() == 4 && fw.size(0) == B && fw.size(1) == 2 &&
+                fw.size(2) == H && fw.size(3) == W &&
+                fw.sizes() == bw.sizes(),
+                "flows must both be [B,2,H,W] of the images' B, H, W");
+    TORCH_CHECK(occ_fw.dim() == 4 && occ_fw.size(0) == B &&
+                occ_fw.size(1) == 1 && occ_fw.size(2) == H &&
+                occ_fw.size(3) == W && occ_fw.sizes() == occ_bw.sizes(),
+                "masks must both be [B,1,H,W] of the images' B, H, W");
+    TORCH_CHECK(im0.scalar_type() == at::kFloat &&
+                im1.scalar_type() == at::kFloat &&
+                fw.scalar_type() == at::kFloat &&
+                bw.scalar_type() == at::kFloat,
+                "images and flows must be fp32");
+    TORCH_CHECK(occ_fw.scalar_type() == at::kByte &&
+                occ_bw.scalar_type() == at::kByte, "masks must be uint8");
+    const auto dev = im0.device();
+    TORCH_CHECK(im1.device() == dev && fw.device() == dev &&
+                bw.device() == dev && occ_fw.device() == dev &&
+                occ_bw.device() == dev, "inputs must share one device");
+    TORCH_CHECK(t >= 0.0 && t <= 1.0, "t must lie in [0, 1]");
+    // the source index shares a 64-bit key with the distance bits
+    TORCH_CHECK(H * W < (int64_t(1) << 31), "H*W must be below 2^31");
+    auto frame = at::empty_like(im0);
+    auto flow_t0 = at::empty_like(fw);
+    auto flow_t1 = at::empty_like(fw);
+    auto cover = at::empty({B, 1, H, W}, im0.options().dtype(at::kByte));
+    if (B * H * W == 0) return {frame, flow_t0, flow_t1, cover};
+    auto keys = at::empty({2, B, H, W}, im0.options().dtype(at::kLong));
+    const int err = launch_frame_interp(
+        im0.data_ptr<float>(), im1.data_ptr<float>(), fw.data_ptr<float>(),
+        bw.data_ptr<float>(), occ_fw.data_ptr<unsigned char>(),
+        occ_bw.data_ptr<unsigned char>(),
+        (unsigned long long*)keys.data_ptr<int64_t>(),
+        frame.data_ptr<float>(), flow_t0.data_ptr<float>(),
+        flow_t1.data_ptr<float>(), cover.data_ptr<unsigned char>(), (int)B,
+        (int)C, (int)H, (int)W, (float)t, current_stream());
+    TORCH_CHECK(err == 0, "interpolate_frame: ",
+                hipGetErrorString((hipError_t)err));
+    return {frame, flow_t0, flow_t1, cover};
 }
 
 at::Tensor corr_volume_nhwc_fp8(at::Tensor f1, at::Tensor f2, bool out_bf16) {
@@ -866,6 +931,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "deterministic forward projection of a flow field -> "
           "(projected, holes)",
           py::arg("flow"), py::arg("direction") = 1);
+    m.def("interpolate_frame", &interpolate_frame,
+          "frame at time t from a bidirectional flow pair -> "
+          "(frame, flow_t0, flow_t1, cover)",
+          py::arg("im0"), py::arg("im1"), py::arg("fw"), py::arg("bw"),
+          py::arg("occ_fw_u8"), py::arg("occ_bw_u8"), py::arg("t"));
     m.def("corr_volume_nhwc_fp8", &corr_volume_nhwc_fp8,
           "fp8 e4m3 corr volume (MX-scaled MFMA, per-tensor quant)");
     m.def("corr_volume_nhwc_fp8s", &corr_volume_nhwc_fp8s,

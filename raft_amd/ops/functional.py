@@ -295,3 +295,33 @@ def forward_project(flow: torch.Tensor, direction: int = 1):
             flow.detach().float().contiguous(), direction)
         return out, holes
     return torch_ref.forward_project(flow.detach(), direction)
+
+
+def interpolate_frame(im0: torch.Tensor, im1: torch.Tensor,
+                      flow_fw: torch.Tensor, flow_bw: torch.Tensor,
+                      occ_fw: torch.Tensor, occ_bw: torch.Tensor, t: float):
+    """The frame at time ``t`` in [0, 1] between ``im0`` and ``im1`` from
+    their bidirectional flows and occlusion masks (what
+    ``InferenceEngine.bidirectional`` returns): ``(frame [B,C,H,W] fp32,
+    flow_t0, flow_t1 [B,2,H,W] fp32, cover [B,1,H,W] uint8)``. See
+    torch_ref.interpolate_frame for the definition; the GPU kernels match
+    it bit for bit, are stream-ordered (no host sync) and
+    graph-capturable. Images may be bf16 or fp32 (computed in fp32), masks
+    bool. No autograd. A CUDA tensor without the built extension is an
+    error, not a fall-back to the oracle; ``RAFT_AMD_FORCE_TORCH=1``
+    selects the oracle explicitly."""
+    t = torch_ref._check_interp_args(im0, im1, flow_fw, flow_bw, occ_fw,
+                                     occ_bw, t)
+    args = [a.detach() for a in (im0, im1, flow_fw, flow_bw)]
+    if _use_hip(im0):
+        from raft_amd.ops import require_hip
+        im0, im1, fw, bw = (a.float().contiguous() for a in args)
+        # a bool mask is one 0/1 byte per cell: reinterpret, no copy
+        masks = [(m.contiguous().view(torch.uint8) if m.dtype == torch.bool
+                  else (m != 0).view(torch.uint8)).detach()
+                 for m in (occ_fw, occ_bw)]
+        frame, ft0, ft1, cover = require_hip().interpolate_frame(
+            im0, im1, fw, bw, masks[0], masks[1], t)
+        return frame, ft0, ft1, cover
+    return torch_ref.interpolate_frame(*args, occ_fw.detach(),
+                                       occ_bw.detach(), t)

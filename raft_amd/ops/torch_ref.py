@@ -224,6 +224,36 @@ def fb_consistency(flow_fw: torch.Tensor, flow_bw: torch.Tensor,
     return occ
 
 
+def _splat_keys(tx: torch.Tensor, ty: torch.Tensor):
+    """Nearest-source splat of the targets (tx, ty), each [B,H,W] fp32, of
+    the source cells of a [B,H,W] grid: per cell the minimum 64-bit key
+    (float_bits(d2) << 32) | source_index over the valid targets whose
+    {floor, floor+1}^2 neighbourhood holds the cell (see forward_project).
+    Returns (keys [B*H*W] int64, the value of a cell without candidate)."""
+    B, H, W = tx.shape
+    HW = H * W
+    dev = tx.device
+    valid = (tx >= 0) & (tx <= W - 1) & (ty >= 0) & (ty <= H - 1)
+    x0 = torch.where(valid, tx, torch.zeros_like(tx)).floor()
+    y0 = torch.where(valid, ty, torch.zeros_like(ty)).floor()
+
+    empty = torch.iinfo(torch.int64).max
+    keys = torch.full((B * HW,), empty, dtype=torch.int64, device=dev)
+    src = torch.arange(HW, device=dev, dtype=torch.int64).view(1, H, W)
+    base = (torch.arange(B, device=dev, dtype=torch.int64) * HW) \
+        .view(B, 1, 1)
+    for dy in (0.0, 1.0):
+        for dx in (0.0, 1.0):
+            qx, qy = x0 + dx, y0 + dy
+            ok = valid & (qx <= W - 1) & (qy <= H - 1)
+            ddx, ddy = tx - qx, ty - qy
+            d2 = (ddx * ddx + ddy * ddy).contiguous()
+            key = (d2.view(torch.int32).to(torch.int64) << 32) | src
+            cell = base + (qy * W + qx).long()
+            keys.scatter_reduce_(0, cell[ok], key[ok], reduce="amin")
+    return keys, empty
+
+
 def forward_project(flow: torch.Tensor, direction: int = 1):
     """Deterministic forward projection of a flow field — RAFT's warm start
     (``forward_interpolate``) as a nearest-source splat. This definition is
@@ -269,24 +299,7 @@ def forward_project(flow: torch.Tensor, direction: int = 1):
     fx, fy = f[:, 0], f[:, 1]                            # [B, H, W]
     tx = xs + fx if direction > 0 else xs - fx
     ty = ys + fy if direction > 0 else ys - fy
-    valid = (tx >= 0) & (tx <= W - 1) & (ty >= 0) & (ty <= H - 1)
-    x0 = torch.where(valid, tx, torch.zeros_like(tx)).floor()
-    y0 = torch.where(valid, ty, torch.zeros_like(ty)).floor()
-
-    empty = torch.iinfo(torch.int64).max
-    keys = torch.full((B * HW,), empty, dtype=torch.int64, device=dev)
-    src = torch.arange(HW, device=dev, dtype=torch.int64).view(1, H, W)
-    base = (torch.arange(B, device=dev, dtype=torch.int64) * HW) \
-        .view(B, 1, 1)
-    for dy in (0.0, 1.0):
-        for dx in (0.0, 1.0):
-            qx, qy = x0 + dx, y0 + dy
-            ok = valid & (qx <= W - 1) & (qy <= H - 1)
-            ddx, ddy = tx - qx, ty - qy
-            d2 = (ddx * ddx + ddy * ddy).contiguous()
-            key = (d2.view(torch.int32).to(torch.int64) << 32) | src
-            cell = base + (qy * W + qx).long()
-            keys.scatter_reduce_(0, cell[ok], key[ok], reduce="amin")
+    keys, empty = _splat_keys(tx, ty)
 
     cov = (keys != empty).view(B, H, W)
     winner = (keys & 0xFFFFFFFF).view(B, 1, HW).expand(B, 2, HW)
@@ -329,3 +342,152 @@ def forward_project(flow: torch.Tensor, direction: int = 1):
                        torch.zeros_like(total))
     out = torch.where(cov.unsqueeze(1), val, fill)
     return out, ~cov.unsqueeze(1)
+
+
+def _check_interp_args(im0, im1, flow_fw, flow_bw, occ_fw, occ_bw, t):
+    """Argument contract of interpolate_frame; returns t as a float."""
+    try:
+        t = float(t)
+    except (TypeError, ValueError):
+        raise ValueError(f"t must be a number in [0, 1], got {t!r}")
+    if not 0.0 <= t <= 1.0:           # NaN fails both comparisons
+        raise ValueError(f"t must lie in [0, 1], got {t}")
+    if im0.dim() != 4 or im0.shape[1] < 1 or im0.shape != im1.shape:
+        raise ValueError(f"images must both be [B,C,H,W] with C >= 1, got "
+                         f"{tuple(im0.shape)} and {tuple(im1.shape)}")
+    B, _, H, W = im0.shape
+    for name, f in (("flow_fw", flow_fw), ("flow_bw", flow_bw)):
+        if f.dim() != 4 or tuple(f.shape) != (B, 2, H, W):
+            raise ValueError(f"{name} must be [B,2,H,W] = {(B, 2, H, W)}, "
+                             f"got {tuple(f.shape)}")
+    for name, m in (("occ_fw", occ_fw), ("occ_bw", occ_bw)):
+        if m.dim() != 4 or tuple(m.shape) != (B, 1, H, W):
+            raise ValueError(f"{name} must be [B,1,H,W] = {(B, 1, H, W)}, "
+                             f"got {tuple(m.shape)}")
+    return t
+
+
+def interpolate_frame(im0: torch.Tensor, im1: torch.Tensor,
+                      flow_fw: torch.Tensor, flow_bw: torch.Tensor,
+                      occ_fw: torch.Tensor, occ_bw: torch.Tensor, t: float):
+    """The frame at time t in [0, 1] between ``im0`` (t=0) and ``im1``
+    (t=1), from their bidirectional flows and occlusion masks. This
+    definition is the contract: the HIP kernels (csrc/frame_interp.hip)
+    match it bit for bit.
+
+    im0, im1: [B,C,H,W] (computed in fp32); flow_fw (0->1), flow_bw (1->0):
+    [B,2,H,W] fp32; occ_fw, occ_bw: [B,1,H,W] bool as fb_consistency
+    returns them. Returns (frame [B,C,H,W] fp32, flow_t0, flow_t1
+    [B,2,H,W] fp32, cover [B,1,H,W] uint8: bit 0 = splat A, bit 1 =
+    splat B).
+
+    With tf = float32(t), u = 1 - tf, every product and sum a separately
+    rounded fp32 operation (no FMA), divisions correctly rounded:
+
+    1. Splats (the scatter rules of forward_project): source p of frame 0
+       targets p + tf*flow_fw[p] (A), source p of frame 1 targets
+       p + u*flow_bw[p] (B). Per cell q: coverA, gA = flow_fw[winnerA],
+       coverB, gB = flow_bw[winnerB].
+    2. Ft0 = (-tf)*gA if coverA, else tf*gB if coverB; Ft1 = (-u)*gB if
+       coverB, else u*gA if coverA; with neither, the linear approximation
+       Ft0 = (-(u*tf))*fw[q] + (tf*tf)*bw[q],
+       Ft1 = (u*u)*fw[q] + (-(tf*u))*bw[q].
+    3. x0 = q + Ft0, x1 = q + Ft1; in0 / in1 = inside the frame (NaN is
+       outside); o0 = occ_fw at the cell nearest x0, o1 = occ_bw at the
+       cell nearest x1 (round half to even, clamped, NaN -> 0);
+       v0 = in0 and not o1, v1 = in1 and not o0; (w0, w1) = (u if v0 else
+       0, tf if v1 else 0), and (u, tf) when that sum is 0.
+    4. S0 / S1 = bilinear samples of im0 at x0 / im1 at x1 in the
+       convention of fb_consistency (clamped corners, weights clamped to
+       [0,1], NaN -> corner 0 and weight 0, summed as
+       ((w00*a + w01*b) + w10*c) + w11*d);
+       frame = (w0*S0 + w1*S1) / (w0 + w1).
+
+    t=0 returns im0 and t=1 returns im1 bit for bit (for finite flows);
+    swapping the frames, the flows and the masks and replacing t by 1-t
+    gives the same frame with flow_t0 / flow_t1 exchanged.
+    """
+    t = _check_interp_args(im0, im1, flow_fw, flow_bw, occ_fw, occ_bw, t)
+    a0 = im0.float().contiguous()
+    a1 = im1.float().contiguous()
+    fw = flow_fw.float().contiguous()
+    bw = flow_bw.float().contiguous()
+    B, C, H, W = a0.shape
+    dev = a0.device
+    HW = H * W
+    if B * HW == 0:
+        return (a0.clone(), fw.clone(), bw.clone(),
+                torch.zeros(B, 1, H, W, dtype=torch.uint8, device=dev))
+
+    # the scalars, rounded to fp32 one operation at a time on the host
+    c = torch.tensor([t], dtype=torch.float32)
+    tf = c.item()
+    u = (1.0 - c).item()
+    ut = ((1.0 - c) * c).item()
+    tt = (c * c).item()
+    uu = ((1.0 - c) * (1.0 - c)).item()
+
+    xs = torch.arange(W, device=dev, dtype=torch.float32).view(1, 1, W)
+    ys = torch.arange(H, device=dev, dtype=torch.float32).view(1, H, 1)
+
+    def splat(f, s):
+        keys, empty = _splat_keys(xs + s * f[:, 0], ys + s * f[:, 1])
+        cov = (keys != empty).view(B, 1, H, W)
+        winner = (keys & 0xFFFFFFFF).view(B, 1, HW).expand(B, 2, HW)
+        winner = torch.where(cov.view(B, 1, HW), winner,
+                             torch.zeros_like(winner))
+        return cov, f.view(B, 2, HW).gather(2, winner).view(B, 2, H, W)
+
+    cov_a, g_a = splat(fw, tf)
+    cov_b, g_b = splat(bw, u)
+    ft0 = torch.where(cov_a, (-tf) * g_a, torch.where(
+        cov_b, tf * g_b, (-ut) * fw + tt * bw))
+    ft1 = torch.where(cov_b, (-u) * g_b, torch.where(
+        cov_a, u * g_a, uu * fw + (-ut) * bw))
+    cover = cov_a.to(torch.uint8) | (cov_b.to(torch.uint8) << 1)
+
+    def inside(px, py):
+        return (px >= 0) & (px <= W - 1) & (py >= 0) & (py <= H - 1)
+
+    def nearest(mask, px, py):
+        xr = torch.nan_to_num(px.round(), nan=0.0).clamp(0, W - 1).long()
+        yr = torch.nan_to_num(py.round(), nan=0.0).clamp(0, H - 1).long()
+        idx = (yr * W + xr).view(B, 1, HW)
+        return mask.reshape(B, 1, HW).gather(2, idx).view(B, H, W) != 0
+
+    def sample(img, px, py):
+        x0f = torch.nan_to_num(px.floor(), nan=0.0).clamp(0, W - 1)
+        y0f = torch.nan_to_num(py.floor(), nan=0.0).clamp(0, H - 1)
+        x0, y0 = x0f.long(), y0f.long()
+        x1 = (x0 + 1).clamp(max=W - 1)
+        y1 = (y0 + 1).clamp(max=H - 1)
+        ax = torch.nan_to_num(px - x0f, nan=0.0).clamp(0, 1)
+        ay = torch.nan_to_num(py - y0f, nan=0.0).clamp(0, 1)
+        w00 = ((1 - ax) * (1 - ay)).unsqueeze(1)
+        w01 = (ax * (1 - ay)).unsqueeze(1)
+        w10 = ((1 - ax) * ay).unsqueeze(1)
+        w11 = (ax * ay).unsqueeze(1)
+        flat = img.view(B, C, HW)
+
+        def tap(yi, xi):
+            idx = (yi * W + xi).view(B, 1, HW).expand(B, C, HW)
+            return flat.gather(2, idx).view(B, C, H, W)
+
+        return ((w00 * tap(y0, x0) + w01 * tap(y0, x1))
+                + w10 * tap(y1, x0)) + w11 * tap(y1, x1)
+
+    p0x, p0y = xs + ft0[:, 0], ys + ft0[:, 1]
+    p1x, p1y = xs + ft1[:, 0], ys + ft1[:, 1]
+    o0 = nearest(occ_fw, p0x, p0y)
+    o1 = nearest(occ_bw, p1x, p1y)
+    v0 = inside(p0x, p0y) & ~o1
+    v1 = inside(p1x, p1y) & ~o0
+    zero = torch.zeros((), dtype=torch.float32, device=dev)
+    w0 = torch.where(v0, zero + u, zero)
+    w1 = torch.where(v1, zero + tf, zero)
+    none = (w0 + w1) == 0
+    w0 = torch.where(none, zero + u, w0).unsqueeze(1)
+    w1 = torch.where(none, zero + tf, w1).unsqueeze(1)
+    frame = (w0 * sample(a0, p0x, p0y) + w1 * sample(a1, p1x, p1y)) \
+        / (w0 + w1)
+    return frame, ft0, ft1, cover

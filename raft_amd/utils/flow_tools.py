@@ -79,7 +79,10 @@ def reverse_flow(flow01: np.ndarray, static_mask: Optional[np.ndarray] = None,
     --bidirectional``). For projecting a flow forward along itself on the
     device (RAFT's warm start; nearest source instead of conflict
     averaging, the same four-direction hole fill) use
-    ``raft_amd.ops.forward_project``.
+    ``raft_amd.ops.forward_project``. For ``time_step < 1`` — projecting
+    to an intermediate time to synthesise the frame between two frames —
+    use ``raft_amd.ops.interpolate_frame`` (``InferenceEngine.interpolate``),
+    which does it on the device from both flows and their occlusion masks.
     """
     h, w = flow01.shape[:2]
     f = flow01.astype(np.float64) * time_step
