@@ -71,14 +71,46 @@ class _FC:
 
 
 class _GruDir:
-    def __init__(self, convz, convr, convq):
+    """One GRU direction: z/r gate conv pair + candidate conv over [h | x].
+
+    ctx > 0 hoists the context channels out of the loop. x = [inp(ctx) |
+    rest] and inp is the same in every iteration, so the packed columns
+    [W_h | W_inp | W_rest] of each conv are split: ``precompute`` runs the
+    W_inp part of z, r and q once per pair as one stacked conv (fp32 out,
+    biases folded in), and the per-iteration convs read only [h | rest] —
+    the rest slice of x in place — starting from their slice of that
+    term."""
+
+    def __init__(self, convz, convr, convq, ctx: int = 0):
         self.zr_w, self.zr_b, self.kh, self.kw = pack_zr(convz, convr)
         self.q_w, self.q_b, _, _ = pack_conv(convq)
+        self.ctx = ctx
+        self.hd = hd = self.q_w.shape[1]
+        if ctx:
+            full = torch.cat([self.zr_w, self.q_w], dim=1)  # rows z, r, q
+            self.pre_w = full[..., hd:hd + ctx].contiguous()
+            self.pre_b = torch.cat([self.zr_b, self.q_b]).contiguous()
+            loop = torch.cat([full[..., :hd], full[..., hd + ctx:]], dim=-1)
+            self.zr_w = loop[:, :2 * hd].contiguous()
+            self.q_w = loop[:, 2 * hd:].contiguous()
+            self.zr_b = self.q_b = None          # live in pre
 
-    def __call__(self, hip, h, x):
-        z, rh = hip.fconv_gru_zr(h, x, self.zr_w, self.zr_b, self.kh, self.kw)
-        return hip.fconv_gru_q(rh, x, self.q_w, self.q_b, self.kh, self.kw,
-                               z, h)
+    def precompute(self, hip, x):
+        """[B,H,W,3*hd] fp32: channels [0, 2hd) for zr, [2hd, 3hd) for q."""
+        return hip.fconv_plain_f32(x, self.pre_w, self.pre_b, self.kh,
+                                   self.kw, 0, self.ctx)
+
+    def __call__(self, hip, h, x, pre=None):
+        if not self.ctx:
+            z, rh = hip.fconv_gru_zr(h, x, self.zr_w, self.zr_b, self.kh,
+                                     self.kw)
+            return hip.fconv_gru_q(rh, x, self.q_w, self.q_b, self.kh,
+                                   self.kw, z, h)
+        ctx, rest = self.ctx, x.shape[-1] - self.ctx
+        z, rh = hip.fconv_gru_zr_pre(h, x, self.zr_w, self.kh, self.kw, pre,
+                                     0, ctx, rest)
+        return hip.fconv_gru_q_pre(rh, x, self.q_w, self.kh, self.kw, z, h,
+                                   pre, 2 * self.hd, ctx, rest)
 
 
 def _pack_fp8(wp_bf16, dev):
@@ -112,7 +144,7 @@ class _GruDirFP8:
 class FusedBasicUpdate:
     """Packed raft-things update block (motion enc + SepConvGRU + heads)."""
 
-    def __init__(self, ub, corr_cpad: int, ctx_dim: int):
+    def __init__(self, ub, corr_cpad: int, ctx_dim: int, hoist: bool = False):
         enc = ub.encoder
         self.c1 = _FC(enc.convc1, pad_cin=corr_cpad)
         self.c2 = _FC(enc.convc2)
@@ -130,8 +162,13 @@ class FusedBasicUpdate:
             self.gru2 = _GruDirFP8(ub.gru.convz2, ub.gru.convr2,
                                    ub.gru.convq2)
         else:
-            self.gru1 = _GruDir(ub.gru.convz1, ub.gru.convr1, ub.gru.convq1)
-            self.gru2 = _GruDir(ub.gru.convz2, ub.gru.convr2, ub.gru.convq2)
+            hc = ctx_dim if hoist else 0
+            self.gru1 = _GruDir(ub.gru.convz1, ub.gru.convr1, ub.gru.convq1,
+                                hc)
+            self.gru2 = _GruDir(ub.gru.convz2, ub.gru.convr2, ub.gru.convq2,
+                                hc)
+        # the fp8 GRU quantizes the whole x: it keeps the full-K convs
+        self.hoist = hoist and not self.fp8_gru
         # flow_head.conv1 and mask[0] are both 3x3(128->256) on net: run as
         # ONE N=512 conv; their consumers read strided slices of the result
         self.fh1 = _FC(ub.flow_head.conv1)
@@ -146,7 +183,16 @@ class FusedBasicUpdate:
         self._ev_fork = torch.cuda.Event()
         self._ev_join = torch.cuda.Event()
 
-    def __call__(self, hip, net, x_buf, corr_pad, coords1, final=True):
+    def precompute(self, hip, x_buf):
+        """The loop-invariant context terms of the GRU convs (one fp32
+        tensor per direction), or None without the hoist."""
+        if not self.hoist:
+            return None
+        return (self.gru1.precompute(hip, x_buf),
+                self.gru2.precompute(hip, x_buf))
+
+    def __call__(self, hip, net, x_buf, corr_pad, coords1, final=True,
+                 pre=None):
         # motion encoder (model_utils.py:110-119). The flow channels of
         # x_buf were already written by the lookup kernel (fused flow out).
         # The corr branch (c1->c2) and flow branch (f1->f2) are
@@ -183,6 +229,9 @@ class FusedBasicUpdate:
             x8 = hip.quant_fp8(x_buf, ax)
             net = self.gru1(hip, net, x8, ax, hip.quant_fp8(net, ax))
             net = self.gru2(hip, net, x8, ax, hip.quant_fp8(net, ax))
+        elif self.hoist:
+            net = self.gru1(hip, net, x_buf, pre[0])
+            net = self.gru2(hip, net, x_buf, pre[1])
         else:
             net = self.gru1(hip, net, x_buf)
             net = self.gru2(hip, net, x_buf)
@@ -209,13 +258,15 @@ class FusedBasicUpdate:
 class FusedSmallUpdate:
     """Packed raft-small update block (motion enc + ConvGRU, no mask)."""
 
-    def __init__(self, ub, corr_cpad: int, ctx_dim: int):
+    def __init__(self, ub, corr_cpad: int, ctx_dim: int, hoist: bool = False):
         enc = ub.encoder
         self.c1 = _FC(enc.convc1, pad_cin=corr_cpad)
         self.f1 = _FC(enc.convf1)                    # Cin=2: small-K direct
         self.f2 = _FC(enc.convf2)
         self.cv = _FC(enc.conv)                      # in: [cor(96)|flo(32)]
-        self.gru = _GruDir(ub.gru.convz, ub.gru.convr, ub.gru.convq)
+        self.hoist = hoist
+        self.gru = _GruDir(ub.gru.convz, ub.gru.convr, ub.gru.convq,
+                           ctx_dim if hoist else 0)
         self.fh1 = _FC(ub.flow_head.conv1)
         self.fh2 = _FC(ub.flow_head.conv2)
         self.ctx_dim = ctx_dim
@@ -224,7 +275,11 @@ class FusedSmallUpdate:
         self._ev_join = torch.cuda.Event()
         # x = [inp(ctx) | motion(80) | flow(2)]; motion encoder out = 80
 
-    def __call__(self, hip, net, x_buf, corr_pad, coords1, final=True):
+    def precompute(self, hip, x_buf):
+        return self.gru.precompute(hip, x_buf) if self.hoist else None
+
+    def __call__(self, hip, net, x_buf, corr_pad, coords1, final=True,
+                 pre=None):
         ctx = self.ctx_dim
         side = self.side_stream
         if side is not None and not torch.cuda.is_current_stream_capturing():
@@ -247,7 +302,7 @@ class FusedSmallUpdate:
                                     ctx + 80, 2, 1)
             flo = self.f2(hip, flo1)
         self.cv(hip, cor, flo, ACT_RELU, out=x_buf, n_off=ctx)   # 80 ch
-        net = self.gru(hip, net, x_buf)
+        net = self.gru(hip, net, x_buf, pre)
         h1 = self.fh1(hip, net)
         coords_new = hip.fconv_dflow_coords(h1, self.fh2.wp, self.fh2.bias,
                                             coords1, 3, 3)
@@ -391,15 +446,22 @@ class FusedRaft:
         K = 2 * cfg.corr_radius + 1
         self.corr_c = cfg.corr_levels * K * K
         self.corr_cpad = _pad8(self.corr_c)
+        import os
+        # RAFT_AMD_GRU_HOIST (default 1): compute the context part of the
+        # GRU convs once per pair instead of in every iteration; 0 = the
+        # full-K convs. Read here, so one process can hold both variants.
+        # The in-place slice read needs a 16-byte aligned context width.
+        hoist = (os.environ.get("RAFT_AMD_GRU_HOIST", "1") != "0"
+                 and cfg.context_dim % 8 == 0)
         if cfg.small:
             self.update = FusedSmallUpdate(model.update_block, self.corr_cpad,
-                                           cfg.context_dim)
+                                           cfg.context_dim, hoist)
             self.x_dim = cfg.context_dim + 82
         else:
             self.update = FusedBasicUpdate(model.update_block, self.corr_cpad,
-                                           cfg.context_dim)
+                                           cfg.context_dim, hoist)
             self.x_dim = cfg.context_dim + 128
-        import os
+        self.gru_hoist = self.update.hoist
         self.fuse_enc = os.environ.get("RAFT_AMD_EAGER_ENC", "0") != "1"
         if self.fuse_enc:
             fnorm = "instance"
@@ -428,6 +490,10 @@ class FusedRaft:
                                device=net.device, dtype=torch.bfloat16)
         flow_off = self.x_dim - 2      # flow channels of the GRU input
         mask = None
+        # the context channels of x_buf never change inside the loop: their
+        # share of the GRU pre-activations is computed once, here, so it is
+        # part of a captured loop and reads the graph's static x_buf
+        pre = self.update.precompute(hip, x_buf)
         for it in range(iters):
             # lookup writes the taps AND flow = coords1 - grid directly
             # into the GRU input buffer's flow slice (zero glue kernels)
@@ -438,7 +504,8 @@ class FusedRaft:
                                                     None))
             net, mask, coords1 = self.update(hip, net, x_buf, corr_pad,
                                              coords1,
-                                             final=(it == iters - 1))
+                                             final=(it == iters - 1),
+                                             pre=pre)
 
         flow = coords1 - coords0                         # [B,H,W,2] fp32
         if cfg.small:

@@ -85,9 +85,10 @@ void launch_corr_lookup_nhwc_bwd(float* const*, const int*, const int*,
 void launch_corr_pool2x_bf16(const void*, void*, int, int, int, int,
                              long long, hipStream_t);
 void launch_fconv_nhwc_bf16(const void*, int, int, int, const void*, int,
-                            const void*, const float*, void*, int, int, int,
-                            int, int, int, int, int, int, int, const void*,
-                            const void*, void*, void*, int, int, int,
+                            int, int, const void*, const float*, void*, int,
+                            int, int, int, int, int, int, int, int, int,
+                            const void*, const void*, void*, void*,
+                            const float*, int, int, int, int, int,
                             hipStream_t);
 void launch_inorm_stats(const void*, float*, float*, float*, int, int,
                         int, float, hipStream_t);
@@ -793,10 +794,11 @@ at::Tensor fconv_plain(at::Tensor in1, c10::optional<at::Tensor> in2,
         n_off = 0;
     }
     launch_fconv_nhwc_bf16(in1.data_ptr(), C1, in1_stride, (int)in1_off,
-                           p2, C2, wp.data_ptr(), bptr, out.data_ptr(), B,
-                           Ho, Wo, N, (int)n_off, cstride, (int)kh, (int)kw,
-                           (int)act, mode, res_ptr, nullptr, nullptr,
-                           nullptr, (int)alltaps, (int)mtiles, (int)stride,
+                           p2, C2, C2, 0, wp.data_ptr(), bptr,
+                           out.data_ptr(), B, Ho, Wo, N, (int)n_off, cstride,
+                           (int)kh, (int)kw, (int)act, mode, res_ptr,
+                           nullptr, nullptr, nullptr, nullptr, 0, 0,
+                           (int)alltaps, (int)mtiles, (int)stride,
                            current_stream());
     return out;
 }
@@ -811,10 +813,11 @@ std::vector<at::Tensor> fconv_gru_zr(at::Tensor h, at::Tensor x,
     auto z = at::empty_like(h);
     auto rh = at::empty_like(h);
     launch_fconv_nhwc_bf16(h.data_ptr(), hd, hd, 0, x.data_ptr(),
-                           x.size(3), wp.data_ptr(), bias.data_ptr<float>(),
-                           nullptr, B, H, W, N, 0, 0, (int)kh, (int)kw, 0,
-                           1, h.data_ptr(), nullptr, z.data_ptr(),
-                           rh.data_ptr(), -1, -1, 1, current_stream());
+                           x.size(3), x.size(3), 0, wp.data_ptr(),
+                           bias.data_ptr<float>(), nullptr, B, H, W, N, 0, 0,
+                           (int)kh, (int)kw, 0, 1, h.data_ptr(), nullptr,
+                           z.data_ptr(), rh.data_ptr(), nullptr, 0, 0, -1,
+                           -1, 1, current_stream());
     return {z, rh};
 }
 
@@ -828,11 +831,124 @@ at::Tensor fconv_gru_q(at::Tensor rh, at::Tensor x, at::Tensor wp,
     TORCH_CHECK(wp.size(1) == hd);
     auto out = at::empty_like(h);
     launch_fconv_nhwc_bf16(rh.data_ptr(), hd, hd, 0, x.data_ptr(),
-                           x.size(3), wp.data_ptr(),
+                           x.size(3), x.size(3), 0, wp.data_ptr(),
                            bias.data_ptr<float>(), out.data_ptr(), B, H, W,
                            hd, 0, hd, (int)kh, (int)kw, 0, 2, h.data_ptr(),
-                           z.data_ptr(), nullptr, nullptr, -1, -1, 1,
+                           z.data_ptr(), nullptr, nullptr, nullptr, 0, 0,
+                           -1, -1, 1, current_stream());
+    return out;
+}
+
+// ---- GRU convs with the constant part of the input hoisted out.
+// x = [inp | rest]: conv([h | x]) = conv([h | rest]) + conv(inp), and inp
+// (the context features) is the same in every refinement iteration. The
+// second term is computed once (fconv_plain_f32, bias included) and handed
+// in as `pre`; the per-iteration conv reads the rest slice of x in place.
+
+// fp32 conv output, no activation: [B,H,W,N] float
+at::Tensor fconv_plain_f32(at::Tensor in1, at::Tensor wp,
+                           c10::optional<at::Tensor> bias, int64_t kh,
+                           int64_t kw, int64_t in1_off, int64_t in1_len) {
+    CHECK_DEV(in1); CHECK_CONT(in1); CHECK_DEV(wp); CHECK_CONT(wp);
+    TORCH_CHECK(in1.scalar_type() == at::kBFloat16 &&
+                wp.scalar_type() == at::kBFloat16, "fconv needs bf16");
+    TORCH_CHECK((kh == 1 && kw == 1) || (kh == 3 && kw == 3) ||
+                (kh == 1 && kw == 5) || (kh == 5 && kw == 1),
+                "fconv: unsupported kernel shape ", kh, "x", kw);
+    const int B = in1.size(0), H = in1.size(1), W = in1.size(2);
+    const int in1_stride = in1.size(3);
+    const int C1 = in1_len > 0 ? (int)in1_len : in1_stride;
+    TORCH_CHECK(in1_off >= 0 && in1_off % 8 == 0 &&
+                in1_off + C1 <= in1_stride, "in1 slice out of bounds or "
+                "not 16-byte aligned");
+    const int N = wp.size(1);
+    TORCH_CHECK(wp.size(0) == kh * kw && wp.size(2) == C1,
+                "packed weight shape mismatch");
+    const float* bptr = nullptr;
+    if (bias.has_value()) {
+        CHECK_DEV(bias.value()); CHECK_CONT(bias.value());
+        TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() == N);
+        bptr = bias->data_ptr<float>();
+    }
+    auto out = at::empty({B, H, W, N}, in1.options().dtype(at::kFloat));
+    launch_fconv_nhwc_bf16(in1.data_ptr(), C1, in1_stride, (int)in1_off,
+                           nullptr, 0, 0, 0, wp.data_ptr(), bptr,
+                           out.data_ptr(), B, H, W, N, 0, N, (int)kh, (int)kw,
+                           0, 4 /* EP_PLAIN_F32 */, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, 0, 0, -1, -1, 1,
                            current_stream());
+    return out;
+}
+
+// shared argument checks of the two hoisted GRU convs; N = output channels
+static void check_gru_pre(const at::Tensor& h, const at::Tensor& x,
+                          const at::Tensor& wp, const at::Tensor& pre,
+                          int64_t pre_off, int64_t x_off, int64_t x_len,
+                          int64_t N) {
+    TORCH_CHECK(h.scalar_type() == at::kBFloat16 &&
+                x.scalar_type() == at::kBFloat16 &&
+                wp.scalar_type() == at::kBFloat16, "fconv needs bf16");
+    TORCH_CHECK(x.dim() == 4 && x.size(0) == h.size(0) &&
+                x.size(1) == h.size(1) && x.size(2) == h.size(2),
+                "x and h disagree in B/H/W");
+    TORCH_CHECK(x_off % 8 == 0, "x_off must be a multiple of 8 (16-byte "
+                "vector loads), got ", x_off);
+    TORCH_CHECK(x_off >= 0 && x_len > 0 && x_off + x_len <= x.size(3),
+                "x slice [", x_off, ", ", x_off + x_len, ") exceeds ",
+                x.size(3), " channels");
+    TORCH_CHECK(wp.size(2) == h.size(3) + x_len,
+                "packed weight must have hd + x_len input channels");
+    CHECK_DEV(pre);
+    TORCH_CHECK(pre.scalar_type() == at::kFloat, "pre must be fp32");
+    TORCH_CHECK(pre.is_contiguous(), "pre must be contiguous");
+    TORCH_CHECK(pre.dim() == 4 && pre.size(0) == h.size(0) &&
+                pre.size(1) == h.size(1) && pre.size(2) == h.size(2),
+                "pre and h disagree in B/H/W");
+    TORCH_CHECK(pre_off >= 0 && pre_off + N <= pre.size(3),
+                "pre_off + N = ", pre_off + N, " exceeds pre's ",
+                pre.size(3), " channels");
+}
+
+std::vector<at::Tensor> fconv_gru_zr_pre(at::Tensor h, at::Tensor x,
+                                         at::Tensor wp, int64_t kh,
+                                         int64_t kw, at::Tensor pre,
+                                         int64_t pre_off, int64_t x_off,
+                                         int64_t x_len) {
+    CHECK_DEV(h); CHECK_CONT(h); CHECK_CONT(x); CHECK_CONT(wp);
+    const int B = h.size(0), H = h.size(1), W = h.size(2), hd = h.size(3);
+    const int N = wp.size(1);
+    TORCH_CHECK(N == 2 * hd, "zr weights must stack [Wz; Wr]");
+    check_gru_pre(h, x, wp, pre, pre_off, x_off, x_len, N);
+    auto z = at::empty_like(h);
+    auto rh = at::empty_like(h);
+    launch_fconv_nhwc_bf16(h.data_ptr(), hd, hd, 0, x.data_ptr(), (int)x_len,
+                           (int)x.size(3), (int)x_off, wp.data_ptr(),
+                           nullptr, nullptr, B, H, W, N, 0, 0, (int)kh,
+                           (int)kw, 0, 1, h.data_ptr(), nullptr,
+                           z.data_ptr(), rh.data_ptr(),
+                           pre.data_ptr<float>(), (int)pre.size(3),
+                           (int)pre_off, -1, -1, 1, current_stream());
+    return {z, rh};
+}
+
+at::Tensor fconv_gru_q_pre(at::Tensor rh, at::Tensor x, at::Tensor wp,
+                           int64_t kh, int64_t kw, at::Tensor z, at::Tensor h,
+                           at::Tensor pre, int64_t pre_off, int64_t x_off,
+                           int64_t x_len) {
+    CHECK_DEV(rh); CHECK_CONT(rh); CHECK_CONT(x); CHECK_CONT(wp);
+    CHECK_CONT(z); CHECK_CONT(h);
+    const int B = rh.size(0), H = rh.size(1), W = rh.size(2);
+    const int hd = rh.size(3);
+    TORCH_CHECK(wp.size(1) == hd);
+    check_gru_pre(rh, x, wp, pre, pre_off, x_off, x_len, hd);
+    auto out = at::empty_like(h);
+    launch_fconv_nhwc_bf16(rh.data_ptr(), hd, hd, 0, x.data_ptr(),
+                           (int)x_len, (int)x.size(3), (int)x_off,
+                           wp.data_ptr(), nullptr, out.data_ptr(), B, H, W,
+                           hd, 0, hd, (int)kh, (int)kw, 0, 2, h.data_ptr(),
+                           z.data_ptr(), nullptr, nullptr,
+                           pre.data_ptr<float>(), (int)pre.size(3),
+                           (int)pre_off, -1, -1, 1, current_stream());
     return out;
 }
 
@@ -964,4 +1080,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fconv_dflow_coords", &fconv_dflow_coords,
           "flow-head final conv fused with the coords update");
     m.def("fconv_gru_q", &fconv_gru_q, "GRU candidate conv + state update");
+    m.def("fconv_plain_f32", &fconv_plain_f32,
+          "NHWC bf16 conv (+bias) with unrounded fp32 output, no activation",
+          py::arg("in1"), py::arg("wp"), py::arg("bias"), py::arg("kh"),
+          py::arg("kw"), py::arg("in1_off") = 0, py::arg("in1_len") = 0);
+    m.def("fconv_gru_zr_pre", &fconv_gru_zr_pre,
+          "GRU z/r conv pair over [h | x[..., x_off:x_off+x_len]] plus the "
+          "fp32 term pre[..., pre_off:pre_off+2*hd] (bias folded in)",
+          py::arg("h"), py::arg("x"), py::arg("wp"), py::arg("kh"),
+          py::arg("kw"), py::arg("pre"), py::arg("pre_off"),
+          py::arg("x_off"), py::arg("x_len"));
+    m.def("fconv_gru_q_pre", &fconv_gru_q_pre,
+          "GRU candidate conv + state update over [rh | x slice] plus the "
+          "fp32 term pre[..., pre_off:pre_off+hd] (bias folded in)",
+          py::arg("rh"), py::arg("x"), py::arg("wp"), py::arg("kh"),
+          py::arg("kw"), py::arg("z"), py::arg("h"), py::arg("pre"),
+          py::arg("pre_off"), py::arg("x_off"), py::arg("x_len"));
 }

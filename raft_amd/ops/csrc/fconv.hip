@@ -15,7 +15,13 @@
 //     fragment order);
 //   * SAME zero padding, arbitrary odd kh x kw (templated per shape);
 //   * epilogue modes: plain activation / GRU z+r (sigmoid, r*h product) /
-//     GRU candidate (tanh + h' = (1-z)h + z*q) — model_utils.py:138-169;
+//     GRU candidate (tanh + h' = (1-z)h + z*q) — model_utils.py:138-169 /
+//     plain fp32 store;
+//   * the second input can be a channel slice of a wider buffer, and the
+//     accumulators can start from an fp32 tensor instead of zero: the GRU
+//     convs read [h | motion | flow] and start from the context channels'
+//     share of the pre-activation, which is the same in every iteration
+//     and computed once per pair with the fp32 store;
 //   * output can be written into a channel-slice of a wider NHWC buffer
 //     (n_off / out_cstride), which is how the per-iteration GRU input
 //     buffer x = [ctx | motion | flow] is assembled without copies.
@@ -78,6 +84,8 @@ RAFT_DEV float factivate(float v, int act) {
 #define EP_GRU_Q 2    // N = hd: h' = (1-z)*h + z*tanh(q)
 #define EP_RES_RELU 3 // out = relu(res + relu(v)) — residual blocks
                       // (res tensor passed via the h_state slot)
+#define EP_PLAIN_F32 4 // out is float*: v stored unrounded, no activation
+                       // (the GRU convs' hoisted context term, see `pre`)
 
 // MI/NJ: per-wave 16x16 fragment repeats; tile = (32*MI) x (32*NJ*2)
 // with the fixed 2x2 wave layout. (2,4) = 64x128 (compute-efficient);
@@ -114,14 +122,23 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
     const __hip_bfloat16* __restrict__ in1, int C1,
     int in1_stride, int in1_off,                      // strided slice of in1
     const __hip_bfloat16* __restrict__ in2, int C2,   // may be null/0
+    int in2_stride,       // in2 = first channel of a slice of such rows
     const __hip_bfloat16* __restrict__ wp,            // [KH*KW][N][C1+C2]
     const float* __restrict__ bias,                   // [N] or null
     __hip_bfloat16* __restrict__ out,                 // NHWC slice target
     int H, int W, int N, int n_off, int out_cstride, int act, int mode,
+    int pre_stride,                                   // see pre
     const __hip_bfloat16* __restrict__ h_state,       // [B,H,W,hd] (GRU)
-    const __hip_bfloat16* __restrict__ z_buf_in,      // [B,H,W,hd] (EP_GRU_Q)
-    __hip_bfloat16* __restrict__ z_buf_out,           // [B,H,W,hd] (EP_GRU_ZR)
-    __hip_bfloat16* __restrict__ rh_out) {            // [B,H,W,hd] (EP_GRU_ZR)
+    // [B,H,W,hd] z gate: written by EP_GRU_ZR, read by EP_GRU_Q. One
+    // slot for both keeps the explicit arguments within 128 bytes.
+    __hip_bfloat16* __restrict__ z_buf,
+    __hip_bfloat16* __restrict__ rh_out,              // [B,H,W,hd] (EP_GRU_ZR)
+    // fp32 per-position term the accumulators start from,
+    // pre[p * pre_stride + n] (a channel slice of rows of pre_stride
+    // floats, pre at its first channel): for the GRU convs the part of
+    // the conv over input channels that stay the same in every iteration,
+    // computed once (EP_PLAIN_F32, bias folded in). Null: none.
+    const float* __restrict__ pre) {
     constexpr int TAPS = KH * KW;
     constexpr int BM = 32 * MI;          // block output positions
     constexpr int BN = 32 * NJ;          // block output channels
@@ -165,6 +182,29 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 acc[mt][i][j] = {0.f, 0.f, 0.f, 0.f};
+    // a hoisted term: the accumulators start from it, so the loads'
+    // latency hides under the k-loop (same indexing as the epilogue;
+    // adding it there instead measured 0.16 ms/step slower on the headline
+    // config — profiles/gru_hoist.md). Block-uniform branch.
+    if (pre) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int i = 0; i < MI; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int m = wm + i * 16 + (lane >> 4) * 4 + r;
+                        const int n = n0 + wn + j * 16 + (lane & 15);
+                        const int yy2 = y + m / BMX;
+                        const int x = x0 + mt * BMX + m % BMX;
+                        if (x < W && n < N && yy2 < H)
+                            acc[mt][i][j][r] = pre[
+                                (((long long)b * H + yy2) * W + x) *
+                                pre_stride + n];
+                    }
+    }
 
     char* const sAbase = smem;
     char* const sBbase = smem + NSLAB * ABYTES;
@@ -189,7 +229,7 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
         if (a_one && a_rows && a_cols && S == 1) {
             const bool use1 = k0 + FC_BK <= C1;
             const __hip_bfloat16* src = use1 ? in1 : in2;
-            const int cs = use1 ? in1_stride : C2;
+            const int cs = use1 ? in1_stride : in2_stride;
             const int co = use1 ? (in1_off + k0) : (k0 - C1);
             for (int e = tid; e < NSLAB * AW * (FC_BK / 8); e += 256) {
                 const int sl = e / (AW * (FC_BK / 8));
@@ -234,19 +274,21 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
                             const int kk = k + u;
                             tmp[u] = (kk < C1)
                                    ? in1[p * in1_stride + in1_off + kk]
-                                   : (kk - C1 < C2 ? in2[p * C2 + kk - C1]
-                                                   : (__hip_bfloat16)0.f);
+                                   : (kk - C1 < C2
+                                          ? in2[p * in2_stride + kk - C1]
+                                          : (__hip_bfloat16)0.f);
                         }
                         v = *(const uint4v*)tmp;
                     }
                 } else if (k - C1 < C2) {
                     if (k - C1 + 8 <= C2)
-                        v = *(const uint4v*)(in2 + p * C2 + (k - C1));
+                        v = *(const uint4v*)(in2 + p * in2_stride
+                                             + (k - C1));
                     else {
                         __hip_bfloat16 tmp[8];
                         for (int u = 0; u < 8; ++u) {
                             const int kk = k - C1 + u;
-                            tmp[u] = kk < C2 ? in2[p * C2 + kk]
+                            tmp[u] = kk < C2 ? in2[p * in2_stride + kk]
                                              : (__hip_bfloat16)0.f;
                         }
                         v = *(const uint4v*)tmp;
@@ -366,7 +408,7 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
             if (S == 1 && a_one && a_rows && a_cols) {
                 const bool use1 = k0 + FC_BK <= C1;
                 const __hip_bfloat16* src = use1 ? in1 : in2;
-                const int cs = use1 ? in1_stride : C2;
+                const int cs = use1 ? in1_stride : in2_stride;
                 const int co = use1 ? (in1_off + k0) : (k0 - C1);
 #pragma unroll
                 for (int r = 0; r < RA; ++r) {
@@ -419,20 +461,21 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
                                     tmp[u] = (kk < C1)
                                         ? in1[p * in1_stride + in1_off + kk]
                                         : (kk - C1 < C2
-                                               ? in2[p * C2 + kk - C1]
+                                               ? in2[p * in2_stride + kk - C1]
                                                : (__hip_bfloat16)0.f);
                                 }
                                 v = *(const uint4v*)tmp;
                             }
                         } else if (k - C1 < C2) {
                             if (k - C1 + 8 <= C2)
-                                v = *(const uint4v*)(in2 + p * C2 + (k - C1));
+                                v = *(const uint4v*)(
+                                    in2 + p * in2_stride + (k - C1));
                             else {
                                 __hip_bfloat16 tmp[8];
                                 for (int u = 0; u < 8; ++u) {
                                     const int kk = k - C1 + u;
                                     tmp[u] = kk < C2
-                                        ? in2[p * C2 + kk]
+                                        ? in2[p * in2_stride + kk]
                                         : (__hip_bfloat16)0.f;
                                 }
                                 v = *(const uint4v*)tmp;
@@ -556,10 +599,12 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
                     const float res = (float)h_state[p * hd + n];
                     out[p * out_cstride + n_off + n] = (__hip_bfloat16)
                         fmaxf(res + fmaxf(v, 0.0f), 0.0f);
+                } else if (mode == EP_PLAIN_F32) {
+                    ((float*)out)[p * out_cstride + n_off + n] = v;
                 } else if (mode == EP_GRU_ZR) {
                     const float s = 1.0f / (1.0f + __expf(-v));
                     if (n < hd) {
-                        z_buf_out[p * hd + n] = (__hip_bfloat16)s;
+                        z_buf[p * hd + n] = (__hip_bfloat16)s;
                     } else {
                         const int c = n - hd;
                         rh_out[p * hd + c] = (__hip_bfloat16)(
@@ -567,7 +612,7 @@ __global__ __launch_bounds__(256) void fconv_nhwc_bf16_k(
                     }
                 } else {  // EP_GRU_Q
                     const float q = tanhf(v);
-                    const float z = (float)z_buf_in[p * hd + n];
+                    const float z = (float)z_buf[p * hd + n];
                     const float h = (float)h_state[p * hd + n];
                     out[p * out_cstride + n_off + n] =
                         (__hip_bfloat16)((1.0f - z) * h + z * q);
@@ -810,6 +855,11 @@ struct FconvArgs {
     __hip_bfloat16 *z_buf_out, *rh_out;
     int act;
     hipStream_t s;
+    // not part of FconvShape: none of these steers the pick. in2 and pre
+    // already point at the first channel of their slice.
+    int in2_stride;
+    const float* pre;
+    int pre_stride;
 };
 
 template <int KH, int KW, int MI, int NJ, bool AT, int MT, int S, int TH,
@@ -825,9 +875,12 @@ static bool fc_try(const FconvPick& p, const FconvShape& sh,
     hipLaunchKernelGGL(
         (fconv_nhwc_bf16_k<KH, KW, MI, NJ, AT, MT, S, TH, PIPE>),
         dim3(g[0], g[1], g[2]), dim3(256), 0, a.s, a.in1, sh.C1,
-        sh.in1_stride, sh.in1_off, a.in2, sh.C2, a.wp, a.bias, a.out, sh.H,
-        sh.W, sh.N, sh.n_off, sh.out_cstride, a.act, sh.mode, a.h_state,
-        a.z_buf_in, a.z_buf_out, a.rh_out);
+        sh.in1_stride, sh.in1_off, a.in2, sh.C2, a.in2_stride, a.wp, a.bias,
+        a.out, sh.H, sh.W, sh.N, sh.n_off, sh.out_cstride, a.act, sh.mode,
+        a.pre_stride, a.h_state,
+        sh.mode == EP_GRU_ZR ? a.z_buf_out
+                             : const_cast<__hip_bfloat16*>(a.z_buf_in),
+        a.rh_out, a.pre);
     return true;
 }
 
@@ -882,21 +935,28 @@ static bool fc_try_s2(const FconvPick& p, const FconvShape& sh,
 
 extern "C" void launch_fconv_nhwc_bf16(
     const void* in1, int C1, int in1_stride, int in1_off, const void* in2,
-    int C2, const void* wp, const float* bias, void* out, int B, int H,
-    int W, int N, int n_off, int out_cstride, int kh, int kw, int act,
-    int mode, const void* h_state, const void* z_buf_in, void* z_buf_out,
-    void* rh_out, int alltaps, int mtiles, int stride, hipStream_t s) {
-    // H, W are OUTPUT dims (stride 2: input = 2H x 2W)
+    int C2, int in2_stride, int in2_off, const void* wp, const float* bias,
+    void* out, int B, int H, int W, int N, int n_off, int out_cstride,
+    int kh, int kw, int act, int mode, const void* h_state,
+    const void* z_buf_in, void* z_buf_out, void* rh_out, const float* pre,
+    int pre_stride, int pre_off, int alltaps, int mtiles, int stride,
+    hipStream_t s) {
+    // H, W are OUTPUT dims (stride 2: input = 2H x 2W). mode EP_PLAIN_F32:
+    // out is a float buffer (n_off / out_cstride in floats).
     const FconvShape sh{B, H, W, N, C1, in1_stride, in1_off, C2,
                         in2 != nullptr, kh, kw, stride, mode, n_off,
                         out_cstride};
     const FconvPick p = fconv_pick(sh, alltaps, mtiles, fconv_knobs());
-    const FconvArgs a{(const __hip_bfloat16*)in1, (const __hip_bfloat16*)in2,
+    // the slice offsets of in2 and pre are folded into the pointers (the
+    // kernel is short of scalar registers, not of address arithmetic)
+    const FconvArgs a{(const __hip_bfloat16*)in1,
+                      in2 ? (const __hip_bfloat16*)in2 + in2_off : nullptr,
                       (const __hip_bfloat16*)wp, bias, (__hip_bfloat16*)out,
                       (const __hip_bfloat16*)h_state,
                       (const __hip_bfloat16*)z_buf_in,
                       (__hip_bfloat16*)z_buf_out, (__hip_bfloat16*)rh_out,
-                      act, s};
+                      act, s, in2_stride, pre ? pre + pre_off : nullptr,
+                      pre_stride};
     const dim3 blk(256);
     switch (p.kind) {
     case FCONV_TINYN: {

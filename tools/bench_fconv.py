@@ -95,7 +95,31 @@ def main():
             z, rh = hip.fconv_gru_zr(h, xb, wzr, bzr, kh, kw)
             return hip.fconv_gru_q(rh, xb, wq, bq, kh, kw, z, h)
 
-        print(f"gru {tag}: {bench(gru_pass):.1f} us/pass")
+        # the same pass with the context channels hoisted (K = 384 -> 256:
+        # [h | x[..., ctx:]] read in place, plus the fp32 term), and the
+        # once-per-pair conv that produces that term
+        ctx = 128
+        wzr_l = torch.cat([wzr[..., :hd], wzr[..., hd + ctx:]], -1) \
+            .contiguous()
+        wq_l = torch.cat([wq[..., :hd], wq[..., hd + ctx:]], -1).contiguous()
+        w_pre = torch.cat([wzr, wq], 1)[..., hd:hd + ctx].contiguous()
+        b_pre = torch.cat([bzr, bq])
+        pre = hip.fconv_plain_f32(xb, w_pre, b_pre, kh, kw, 0, ctx)
+
+        def gru_pass_hoisted():
+            z, rh = hip.fconv_gru_zr_pre(h, xb, wzr_l, kh, kw, pre, 0, ctx,
+                                         xd - ctx)
+            return hip.fconv_gru_q_pre(rh, xb, wq_l, kh, kw, z, h, pre,
+                                       2 * hd, ctx, xd - ctx)
+
+        t_zr = bench(lambda: hip.fconv_gru_zr(h, xb, wzr, bzr, kh, kw))
+        t_zr_h = bench(lambda: hip.fconv_gru_zr_pre(
+            h, xb, wzr_l, kh, kw, pre, 0, ctx, xd - ctx))
+        print(f"gru {tag}: {bench(gru_pass):.1f} us/pass"
+              f"   hoisted: {bench(gru_pass_hoisted):.1f} us/pass"
+              f"   (zr alone {t_zr:.1f} -> {t_zr_h:.1f})"
+              f"   precompute {kh}x{kw} C={ctx} N={3 * hd} f32: "
+              f"{bench(lambda: hip.fconv_plain_f32(xb, w_pre, b_pre, kh, kw, 0, ctx)):.1f} us")
 
     # small-Cin specialized kernels (dispatch selected by env at import —
     # rerun the script under RAFT_AMD_SMALLC_MFMA=0 / RAFT_AMD_STEM=0 to
