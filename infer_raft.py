@@ -26,8 +26,8 @@ Modes:
 Flags mirror the reference (infer_raft.py:51-67): --gpu --data --load
 -m/--mode --out --batch -o/--optimizer --im1 --im2 --small, plus the
 rebuild's --iters/--size/--dtype/--steps/--warm/--bidirectional/--stream/
---interp/--workers/--resume/--save-every/--accum (iters was hard-coded 20
-in the reference, networks/RAFT.py:33).
+--interp/--tol/--check-every/--min-iters/--workers/--resume/--save-every/
+--accum (iters was hard-coded 20 in the reference, networks/RAFT.py:33).
 """
 import argparse
 import json
@@ -90,6 +90,15 @@ def parse_args(argv=None):
                         "raft_interp_*_tK.png next to the flow output; "
                         "implies --bidirectional; with --stream they come "
                         "from the session (between)")
+    p.add_argument("--tol", type=float, default=None, metavar="PX",
+                   help="test mode: stop the refinement loop once its "
+                        "update is within PX full-resolution pixels (one "
+                        "final iteration follows); --iters is then the "
+                        "budget. The executed count is printed per pair")
+    p.add_argument("--check-every", type=int, default=4, metavar="K",
+                   help="with --tol: measure the update every K iterations")
+    p.add_argument("--min-iters", type=int, default=1, metavar="M",
+                   help="with --tol: no check before iteration M")
     p.add_argument("--workers", type=int, default=0,
                    help="parallel decode workers for sequence/val modes")
     p.add_argument("--resume", action="store_true",
@@ -111,6 +120,16 @@ def parse_args(argv=None):
         if args.mode != "test":
             p.error("--interp applies to --mode test")
         args.bidirectional = True
+    args.converge = None
+    if args.tol is not None:
+        if args.mode != "test":
+            p.error("--tol applies to --mode test")
+        try:
+            args.converge = raft_amd.Convergence(
+                tol=args.tol, every=args.check_every,
+                min_iters=args.min_iters)
+        except ValueError as e:
+            p.error(str(e))
     return args
 
 
@@ -217,6 +236,11 @@ def mode_test(args, device):
                               m[j, 0].cpu().numpy().astype(np.uint8) * 255)
                 print(f"wrote {stem}_bw.png and {occ}_fw.png / _bw.png")
 
+    def _ran(n):
+        # the executed count, for gated runs only (--tol): an ungated pair
+        # line stays as it was
+        return (f"{n} iters",) if args.converge is not None else ()
+
     times = [k / (args.interp + 1) for k in range(1, args.interp + 1)]
 
     def _write_interp(i, frames_t):
@@ -240,7 +264,8 @@ def mode_test(args, device):
             print("--stream decodes frames as they are pushed: --workers "
                   "ignored")
         session = engine.stream(warm=args.warm,
-                                bidirectional=args.bidirectional)
+                                bidirectional=args.bidirectional,
+                                converge=args.converge)
         for k, path in enumerate(frames):
             img = load_image(path)
             if size is not None:
@@ -254,7 +279,8 @@ def mode_test(args, device):
             if device.type == "cuda":
                 torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            print(k - 1, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
+            print(k - 1, tuple(flow.shape), f"{dt * 1e3:.1f} ms",
+                  *_ran(session.last_iters))
             _write(k - 1, flow, bidir)
             if times:
                 _write_interp(k - 1, session.between(times))
@@ -272,16 +298,19 @@ def mode_test(args, device):
         t0 = time.perf_counter()
         bidir = None
         if args.bidirectional:
-            bidir = engine.bidirectional(im1, im2, flow_init=flow_init)
+            bidir = engine.bidirectional(im1, im2, flow_init=flow_init,
+                                         converge=args.converge)
             flow = bidir.flow_fw
             prev_bw = bidir.flow_bw.float()
         else:
-            flow = engine(im1, im2, flow_init=flow_init)
+            flow = engine(im1, im2, flow_init=flow_init,
+                          converge=args.converge)
         prev_flow = flow.float()
         if device.type == "cuda":
             torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(i, tuple(flow.shape), f"{dt * 1e3:.1f} ms")
+        print(i, tuple(flow.shape), f"{dt * 1e3:.1f} ms",
+              *_ran(engine.last_info.iters_run))
         _write(i, flow, bidir)
         if times:
             from raft_amd.engine.inference import interpolate_between

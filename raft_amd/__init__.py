@@ -22,4 +22,5 @@ file:line it mirrors) and serve as the golden oracle for HIP kernel tests.
 
 __version__ = "0.2.0"
 
+from raft_amd.convergence import Convergence, ConvergenceInfo  # noqa: F401
 from raft_amd.models.raft import RAFT, RaftConfig  # noqa: F401

@@ -15,6 +15,8 @@ from typing import Dict, NamedTuple, Optional, Tuple
 import torch
 import torch.nn.functional as F
 
+from raft_amd.convergence import ConvergenceInfo
+
 
 def pad8(x: torch.Tensor) -> Tuple[torch.Tensor, Tuple[int, int]]:
     """Pad H, W up to multiples of 8 (bottom/right, replicate edges so the
@@ -106,16 +108,23 @@ class InferenceEngine:
         self.use_graph = use_graph and self.device.type == "cuda"
         self.max_graphs = max_graphs
         self._graphs: Dict[Tuple[int, int, int], tuple] = {}
+        self.last_info = None   # ConvergenceInfo of the last call
 
     @torch.no_grad()
     def __call__(self, image1: torch.Tensor, image2: torch.Tensor,
                  iters: Optional[int] = None,
-                 flow_init=None, bidirectional: bool = False):
+                 flow_init=None, bidirectional: bool = False,
+                 converge=None):
         """flow_init: [B,2,H/8,W/8] warm-start at 1/8 resolution (official
         RAFT 2-view warm start; the BASELINE EPE anchor is quoted with it).
         bidirectional=True returns the unpadded pair (flow_fw, flow_bw)
-        from one shared pass; flow_init is then None or a pair."""
+        from one shared pass; flow_init is then None or a pair.
+        converge: a raft_amd.Convergence turns ``iters`` into a budget (the
+        loop stops once its update is within the tolerance); the call's
+        ConvergenceInfo is kept in ``self.last_info``."""
         iters = iters if iters is not None else self.iters
+        n_run = iters if iters is not None else self.model.cfg.iters
+        self.last_info = ConvergenceInfo(iters_run=n_run)
         image1 = image1.to(self.device, self.dtype, non_blocking=True)
         image2 = image2.to(self.device, self.dtype, non_blocking=True)
         image1, hw = pad8(image1)
@@ -133,9 +142,17 @@ class InferenceEngine:
         if bidirectional:
             # off the fused path this skips whole-model graph capture, as
             # flow_init calls do
-            fw, bw = self.model(image1, image2, iters=iters,
-                                flow_init=flow_init, bidirectional=True)
+            fw, bw, self.last_info = self.model(
+                image1, image2, iters=iters, flow_init=flow_init,
+                bidirectional=True, converge=converge, return_info=True)
             return unpad(fw, hw), unpad(bw, hw)
+        if converge is not None:
+            # a gated call decides its length on the host: like flow_init
+            # calls it bypasses the whole-call graph
+            out, self.last_info = self.model(
+                image1, image2, iters=iters, flow_init=flow_init,
+                converge=converge, return_info=True)
+            return unpad(out, hw)
         if fusable:
             return unpad(self.model(image1, image2, iters=iters,
                                     flow_init=flow_init), hw)
@@ -162,14 +179,14 @@ class InferenceEngine:
     @torch.no_grad()
     def bidirectional(self, image1: torch.Tensor, image2: torch.Tensor,
                       iters: Optional[int] = None, flow_init=None,
-                      alpha1: float = 0.01, alpha2: float = 0.5
-                      ) -> BidirectionalFlow:
+                      alpha1: float = 0.01, alpha2: float = 0.5,
+                      converge=None) -> BidirectionalFlow:
         """Both flows plus forward-backward occlusion masks. The masks are
         computed on the unpadded flows, so "leaves the frame" means the
         real frame, not the pad8 canvas."""
         from raft_amd import ops
         fw, bw = self(image1, image2, iters=iters, flow_init=flow_init,
-                      bidirectional=True)
+                      bidirectional=True, converge=converge)
         occ_fw, occ_bw = ops.fb_consistency(fw.contiguous(), bw.contiguous(),
                                             alpha1, alpha2)
         return BidirectionalFlow(fw, bw, occ_fw, occ_bw)
@@ -177,8 +194,8 @@ class InferenceEngine:
     @torch.no_grad()
     def interpolate(self, image1: torch.Tensor, image2: torch.Tensor,
                     times=(0.5,), iters: Optional[int] = None,
-                    alpha1: float = 0.01, alpha2: float = 0.5
-                    ) -> torch.Tensor:
+                    alpha1: float = 0.01, alpha2: float = 0.5,
+                    converge=None) -> torch.Tensor:
         """Frames between ``image1`` (t=0) and ``image2`` (t=1) at the
         given times in [0, 1]: one ``bidirectional`` pass, then one
         ops.interpolate_frame call per time. Returns [T,B,C,H,W] fp32 in
@@ -189,21 +206,24 @@ class InferenceEngine:
         image1 = image1.to(self.device, self.dtype, non_blocking=True)
         image2 = image2.to(self.device, self.dtype, non_blocking=True)
         bidir = self.bidirectional(image1, image2, iters=iters,
-                                   alpha1=alpha1, alpha2=alpha2)
+                                   alpha1=alpha1, alpha2=alpha2,
+                                   converge=converge)
         return interpolate_between(image1, image2, bidir, times)
 
     def stream(self, warm: bool = True, bidirectional: bool = False,
                iters: Optional[int] = None, alpha1: float = 0.01,
-               alpha2: float = 0.5):
+               alpha2: float = 0.5, converge=None):
         """A VideoFlowSession over this engine: push frames one at a time,
         get the flow from the previous frame to each new one. Every frame
         is encoded once, and ``warm`` starts each pair from the previous
         low-resolution flow projected forward (ops.forward_project).
         alpha1/alpha2: occlusion constants of bidirectional sessions, as
-        in ``bidirectional``."""
+        in ``bidirectional``. converge: a raft_amd.Convergence gating
+        every pair of the session (``session.last_iters``)."""
         from raft_amd.engine.video import VideoFlowSession
         return VideoFlowSession(self, warm=warm, bidirectional=bidirectional,
-                                iters=iters, alpha1=alpha1, alpha2=alpha2)
+                                iters=iters, alpha1=alpha1, alpha2=alpha2,
+                                converge=converge)
 
     def _capture(self, image1, image2, iters):
         in1 = image1.clone()
@@ -270,12 +290,16 @@ class Prefetcher:
         return d1, d2
 
 
-def run_mixed_batch(engine: InferenceEngine, pairs, iters=None):
+def run_mixed_batch(engine: InferenceEngine, pairs, iters=None,
+                    converge=None, return_iters: bool = False):
     """Mixed-batch inference with per-sample dynamic H x W (BASELINE
     config 5): groups same-shape pairs into batches (one kernel-efficient
     call per shape group), preserves input order in the returned list.
 
     pairs: sequence of (im1, im2) tensors [3,H,W] or [1,3,H,W].
+    converge: a raft_amd.Convergence; each shape group is gated on its
+    own. return_iters=True also returns the executed iteration count of
+    every pair (its group's), in input order.
     """
     norm = []
     for im1, im2 in pairs:
@@ -287,10 +311,12 @@ def run_mixed_batch(engine: InferenceEngine, pairs, iters=None):
     for idx, (im1, im2) in enumerate(norm):
         groups.setdefault(tuple(im1.shape[-2:]), []).append(idx)
     out = [None] * len(norm)
+    ran = [None] * len(norm)
     for shape, idxs in groups.items():
         b1 = torch.cat([norm[i][0] for i in idxs], dim=0)
         b2 = torch.cat([norm[i][1] for i in idxs], dim=0)
-        flows = engine(b1, b2, iters=iters)
+        flows = engine(b1, b2, iters=iters, converge=converge)
         for j, i in enumerate(idxs):
             out[i] = flows[j:j + 1]
-    return out
+            ran[i] = engine.last_info.iters_run
+    return (out, ran) if return_iters else out

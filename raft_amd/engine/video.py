@@ -31,14 +31,19 @@ class VideoFlowSession:
     BidirectionalFlow (flows + occlusion masks) for bidirectional
     sessions. Returned tensors stay valid after later pushes.
 
+    ``converge`` (a raft_amd.Convergence) gates the refinement loop of every
+    pair; ``last_iters`` is the number of iterations the last pair ran and
+    ``last_info`` its ConvergenceInfo (set for ungated sessions too).
+
     ``between(times)`` of a bidirectional session returns the in-between
     frames of the last two pushed frames (ops.interpolate_frame).
     """
 
     def __init__(self, engine, warm: bool = True,
                  bidirectional: bool = False, iters: Optional[int] = None,
-                 alpha1: float = 0.01, alpha2: float = 0.5):
+                 alpha1: float = 0.01, alpha2: float = 0.5, converge=None):
         self.engine = engine
+        self.converge = converge
         self.warm = warm
         self.bidirectional = bidirectional
         self.iters = iters if iters is not None else engine.iters
@@ -55,6 +60,8 @@ class VideoFlowSession:
         self.last_low_bw = None
         self._frames = (None, None)   # last two unpadded frames (references)
         self._last_bidir = None       # their BidirectionalFlow
+        self.last_iters = None        # iterations the last pair ran
+        self.last_info = None         # its ConvergenceInfo
 
     # ------------------------------------------------------------------
     def _flow_init(self):
@@ -109,16 +116,21 @@ class VideoFlowSession:
                 res = runner.run_pair(
                     self._prev[0], cur[0], self._prev[1],
                     cur[1] if bidir else None, iters, init, bidir,
-                    return_low=True)
+                    return_low=True, converge=self.converge,
+                    return_info=True)
         else:
             cur = frame
             res = None if self._prev is None else model(
                 self._prev, frame, iters=iters, flow_init=init,
-                bidirectional=bidir, return_low=True)
+                bidirectional=bidir, return_low=True,
+                converge=self.converge, return_info=True)
         self._prev, self._runner, self._shape = cur, runner, shape
         self._frames = (self._frames[1], raw)
         if res is None:
             return None
+        res, self.last_info = res[:-1], res[-1]
+        self.last_iters = self.last_info.iters_run
+        eng.last_info = self.last_info
 
         # clone: a captured loop hands out its static output buffers
         n = 2 if bidir else 1

@@ -25,6 +25,8 @@ from typing import Optional
 
 import torch
 
+from raft_amd.convergence import ConvergenceInfo, Gate
+
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 
 
@@ -470,6 +472,8 @@ class FusedRaft:
             self.cnet_f = FusedEncoder(model.cnet, cnorm)
         self._version = self._weights_version()
         self._graphs = {}
+        self._res_host = {}     # pinned [B,2] landing buffers of _check
+        self.last_info = None
 
     def _weights_version(self) -> int:
         return sum(p._version for p in self.model.parameters())
@@ -483,30 +487,35 @@ class FusedRaft:
         so it is hipGraph-capturable (BASELINE config 5) without MIOpen's
         capture-time workspace fallbacks. Returns (upsampled flow, the
         1/8-resolution flow coords1 - coords0 as [B,H8,W8,2] fp32)."""
-        cfg = self.model.cfg
         hip = self.hip
         B, H8, W8, _ = coords0.shape
         corr_buf = torch.zeros(B, H8, W8, self.corr_cpad,
                                device=net.device, dtype=torch.bfloat16)
-        flow_off = self.x_dim - 2      # flow channels of the GRU input
         mask = None
         # the context channels of x_buf never change inside the loop: their
         # share of the GRU pre-activations is computed once, here, so it is
         # part of a captured loop and reads the graph's static x_buf
         pre = self.update.precompute(hip, x_buf)
         for it in range(iters):
-            # lookup writes the taps AND flow = coords1 - grid directly
-            # into the GRU input buffer's flow slice (zero glue kernels)
-            corr_pad = hip.corr_lookup_nhwc(list(levels), coords1,
-                                            cfg.corr_radius, self.corr_cpad,
-                                            True, corr_buf, x_buf, flow_off,
-                                            getattr(self, "_vol_scale",
-                                                    None))
-            net, mask, coords1 = self.update(hip, net, x_buf, corr_pad,
-                                             coords1,
-                                             final=(it == iters - 1),
-                                             pre=pre)
+            net, mask, coords1 = self._iteration(
+                levels, net, x_buf, corr_buf, coords1, pre,
+                final=(it == iters - 1))
+        return self._upsample(coords0, coords1, mask)
 
+    def _iteration(self, levels, net, x_buf, corr_buf, coords1, pre, final):
+        """One refinement iteration: (net, mask or None, new coords1)."""
+        # lookup writes the taps AND flow = coords1 - grid directly
+        # into the GRU input buffer's flow slice (zero glue kernels)
+        corr_pad = self.hip.corr_lookup_nhwc(
+            list(levels), coords1, self.model.cfg.corr_radius,
+            self.corr_cpad, True, corr_buf, x_buf, self.x_dim - 2,
+            getattr(self, "_vol_scale", None))
+        return self.update(self.hip, net, x_buf, corr_pad, coords1,
+                           final=final, pre=pre)
+
+    def _upsample(self, coords0, coords1, mask):
+        cfg = self.model.cfg
+        hip = self.hip
         flow = coords1 - coords0                         # [B,H,W,2] fp32
         if cfg.small:
             from raft_amd.ops import torch_ref
@@ -583,23 +592,26 @@ class FusedRaft:
 
     @torch.no_grad()
     def run(self, image1, image2, iters, flow_init=None,
-            bidirectional=False, return_low=False):
+            bidirectional=False, return_low=False, converge=None,
+            return_info=False):
         """bidirectional: both directions share one pass — cnet sees both
         frames, the volume kernel stores each tile twice (forward and
         transposed) and the loop runs at batch 2B ([fw | bw]); flow_init
         is then already the [2B,2,H8,W8] concatenation. Returns the pair
         (flow_fw, flow_bw). return_low appends the 1/8-resolution flow(s),
-        see run_pair."""
+        converge / return_info gate the loop, see run_pair."""
         B0 = image1.shape[0]
         fmaps, ctx = self._encode([image1, image2], True,
                                   None if bidirectional else B0)
         return self.run_pair(fmaps[:B0].contiguous(),
                              fmaps[B0:].contiguous(), ctx, None, iters,
-                             flow_init, bidirectional, return_low)
+                             flow_init, bidirectional, return_low, converge,
+                             return_info)
 
     @torch.no_grad()
     def run_pair(self, f1p, f2p, ctx1, ctx2=None, iters=None,
-                 flow_init=None, bidirectional=False, return_low=False):
+                 flow_init=None, bidirectional=False, return_low=False,
+                 converge=None, return_info=False):
         """Pair stage: everything from the correlation volume on, fed with
         encode() results. f1p/f2p: [B,H8,W8,C] feature maps of the two
         frames; ctx1: context of frame 1 — bidirectional runs also need
@@ -608,7 +620,14 @@ class FusedRaft:
         flow_bw); with return_low followed by the 1/8-resolution flow
         [B,2,H8,W8] fp32 (one per direction) — the quantity flow_init
         seeds. Under graph replay the results live in static buffers that
-        the next replay of the same shape overwrites: clone to keep."""
+        the next replay of the same shape overwrites: clone to keep.
+
+        converge: a raft_amd.Convergence makes ``iters`` a budget — the
+        loop checks its coords update (ops.flow_residual on the
+        interleaved coords) and after convergence runs the final
+        iteration and stops; the result equals the ungated call with
+        iters = the executed count bit for bit. return_info appends the
+        ConvergenceInfo, also kept as ``self.last_info``."""
         model = self.model
         cfg = model.cfg
         hip = self.hip
@@ -690,30 +709,50 @@ class FusedRaft:
         use_graph = getattr(model, "_fused_use_graph", None)
         if use_graph is None:
             use_graph = iters <= 16
-        if not use_graph:
+        # a gated call (converge) runs the same iterations one at a time
+        # and measures the coords update at its check iterations; the same
+        # graph policy applies to its budget
+        gate = None
+        info = ConvergenceInfo(iters_run=iters)
+        if converge is not None:
+            gate = Gate(converge, iters, H8 * W8)
+            info = gate.info
+        self.last_info = info
+
+        def eager():
             x_buf = torch.empty(B, H8, W8, self.x_dim, device=net.device,
                                 dtype=torch.bfloat16)
             x_buf[..., :cfg.context_dim] = inp
-            out, low = self._loop(levels, net, x_buf, coords0, coords1,
+            if gate is None:
+                return self._loop(levels, net, x_buf, coords0, coords1,
                                   iters)
-            return self._result(out, low, bidirectional, return_low)
+            return self._loop_gated(levels, net, x_buf, coords0, coords1,
+                                    gate)
+
+        if not use_graph:
+            out, low = eager()
+            return self._result(out, low, bidirectional, return_low,
+                                info if return_info else None)
 
         # a bidirectional run shares the captured loop of a unidirectional
         # batch-2B run (identical kernels) — except under RAFT_AMD_FP8_CORR,
-        # where that graph may hold fp8 level buffers
-        key = (B, H8, W8, iters)
+        # where that graph may hold fp8 level buffers. One (step, tail)
+        # graph pair serves every budget and Convergence of a shape.
+        key = (B, H8, W8, iters if gate is None else "gated")
         if bidirectional and fp8_mode != "0":
             key += ("bf16",)
         entry = self._graphs.get(key)
         if entry is None:
             if len(self._graphs) >= 4:     # shape-bucket cap
-                x_buf = torch.empty(B, H8, W8, self.x_dim,
-                                    device=net.device, dtype=torch.bfloat16)
-                x_buf[..., :cfg.context_dim] = inp
-                out, low = self._loop(levels, net, x_buf, coords0, coords1,
+                out, low = eager()
+                return self._result(out, low, bidirectional, return_low,
+                                    info if return_info else None)
+            if gate is None:
+                entry = self._capture(levels, net, inp, coords0, coords1,
                                       iters)
-                return self._result(out, low, bidirectional, return_low)
-            entry = self._capture(levels, net, inp, coords0, coords1, iters)
+            else:
+                entry = self._capture_gated(levels, net, inp, coords0,
+                                            coords1)
             self._graphs[key] = entry
         graph, st = entry
         for dst, src in zip(st["levels"], levels):
@@ -723,21 +762,113 @@ class FusedRaft:
         st["coords1"].copy_(coords1)
         if st.get("vol_scale") is not None:   # fp8-storage dequant scalar
             st["vol_scale"].copy_(self._vol_scale)
-        graph.replay()
-        return self._result(st["out"], st["low"], bidirectional, return_low)
+        if gate is None:
+            graph.replay()
+        else:
+            self._replay_gated(graph, st, gate)
+        return self._result(st["out"], st["low"], bidirectional, return_low,
+                            info if return_info else None)
 
     @staticmethod
-    def _result(out, low, bidirectional, return_low):
+    def _result(out, low, bidirectional, return_low, info=None):
         """Shape run_pair's return value: out [B,2,H,W], low the loop's
-        [B,H8,W8,2] flow (returned as its logical [B,2,H8,W8] view)."""
+        [B,H8,W8,2] flow (returned as its logical [B,2,H8,W8] view), info
+        the ConvergenceInfo to append (return_info)."""
         h = out.shape[0] // 2
         res = (out[:h], out[h:]) if bidirectional else (out,)
         if return_low:
             low = low.permute(0, 3, 1, 2)
             res += (low[:h], low[h:]) if bidirectional else (low,)
+        if info is not None:
+            res += (info,)
         return res if len(res) > 1 else res[0]
 
-    def _capture(self, levels, net, inp, coords0, coords1, iters):
+    # ------------------------------------------------------ gated loop
+    def _check(self, gate, it, prev, nxt):
+        """Measure the coords update prev -> nxt (interleaved [B,H8,W8,2])
+        of iteration ``it`` and tell whether the loop has converged: one
+        memset + one kernel, one device-to-host copy of the [B,2] result
+        and one wait — the only synchronisation of a gated call."""
+        raw = self.hip.flow_residual(prev.permute(0, 3, 1, 2),
+                                     nxt.permute(0, 3, 1, 2), gate.thr_sq,
+                                     None)
+        B = raw.shape[0]
+        host = self._res_host.get(B)
+        if host is None:
+            host = torch.empty(B, 2, dtype=torch.int32).pin_memory()
+            self._res_host[B] = host
+        host.copy_(raw, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return gate.record_raw(it, host.numpy())
+
+    @torch.no_grad()
+    def _loop_gated(self, levels, net, x_buf, coords0, coords1, gate):
+        """_loop under a convergence gate: non-final iterations up to the
+        decision, then the final one (merged heads + mask) and the
+        upsample — the kernel sequence of _loop with iters = the executed
+        count."""
+        B, H8, W8, _ = coords0.shape
+        corr_buf = torch.zeros(B, H8, W8, self.corr_cpad,
+                               device=net.device, dtype=torch.bfloat16)
+        pre = self.update.precompute(self.hip, x_buf)
+        last = False
+        for it in range(1, gate.budget + 1):
+            final = last or it == gate.budget
+            prev = coords1
+            net, mask, coords1 = self._iteration(levels, net, x_buf,
+                                                 corr_buf, coords1, pre,
+                                                 final=final)
+            if final:
+                break
+            if gate.wants(it):
+                last = self._check(gate, it, prev, coords1)
+        gate.info.iters_run = it
+        return self._upsample(coords0, coords1, mask)
+
+    def _step(self, st):
+        """One non-final iteration on the static buffers (a step graph's
+        body): coords_prev <- coords1, then net and coords1 advance."""
+        st["coords_prev"].copy_(st["coords1"])
+        net, _, coords1 = self._iteration(
+            st["levels"], st["net"], st["x_buf"], st["corr_buf"],
+            st["coords1"], st["pre"], final=False)
+        st["net"].copy_(net)
+        st["coords1"].copy_(coords1)
+
+    def _tail(self, st):
+        """The final iteration and the upsample on the static buffers."""
+        _, mask, coords1 = self._iteration(
+            st["levels"], st["net"], st["x_buf"], st["corr_buf"],
+            st["coords1"], st["pre"], final=True)
+        return self._upsample(st["coords0"], coords1, mask)
+
+    def _set_pre(self, st):
+        """The hoisted context terms of this call into the static buffers
+        the two graphs read (eager: the graphs serve every pair)."""
+        pre = self.update.precompute(self.hip, st["x_buf"])
+        if pre is None:
+            return
+        if isinstance(pre, tuple):
+            for dst, src in zip(st["pre"], pre):
+                dst.copy_(src)
+        else:
+            st["pre"].copy_(pre)
+
+    def _replay_gated(self, graphs, st, gate):
+        step, tail = graphs
+        self._set_pre(st)
+        last = False
+        for it in range(1, gate.budget + 1):
+            if last or it == gate.budget:
+                tail.replay()
+                break
+            step.replay()
+            if gate.wants(it):
+                last = self._check(gate, it, st["coords_prev"],
+                                   st["coords1"])
+        gate.info.iters_run = it
+
+    def _static(self, levels, net, inp, coords0, coords1):
         cfg = self.model.cfg
         st = {
             "levels": [l.clone() for l in levels],
@@ -755,6 +886,37 @@ class FusedRaft:
             st["vol_scale"] = self._vol_scale.clone()
             self._vol_scale = st["vol_scale"]
         st["x_buf"][..., :cfg.context_dim] = inp
+        return st
+
+    def _capture_gated(self, levels, net, inp, coords0, coords1):
+        """Two graphs for a shape: a step graph (one non-final iteration,
+        static net / coords_prev / coords1 in and out) and a tail graph
+        (final iteration + upsample)."""
+        st = self._static(levels, net, inp, coords0, coords1)
+        st["coords_prev"] = coords1.clone()
+        st["corr_buf"] = torch.zeros(net.shape[0], net.shape[1],
+                                     net.shape[2], self.corr_cpad,
+                                     device=net.device,
+                                     dtype=torch.bfloat16)
+        st["pre"] = self.update.precompute(self.hip, st["x_buf"])
+        # warm up on a side stream (allocator steady-state before capture)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self._step(st)
+                self._tail(st)
+        torch.cuda.current_stream().wait_stream(s)
+        step = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(step):
+            self._step(st)
+        tail = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(tail):
+            st["out"], st["low"] = self._tail(st)
+        return (step, tail), st
+
+    def _capture(self, levels, net, inp, coords0, coords1, iters):
+        st = self._static(levels, net, inp, coords0, coords1)
         # warm up on a side stream (allocator steady-state before capture)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())

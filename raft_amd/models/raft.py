@@ -27,6 +27,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from raft_amd import ops
+from raft_amd.convergence import Convergence, ConvergenceInfo, Gate
 from raft_amd.models.encoders import BasicEncoder, SmallEncoder
 from raft_amd.models.layers import coords_grid
 from raft_amd.models.update import BasicUpdateBlock, SmallUpdateBlock
@@ -98,7 +99,8 @@ class RAFT(nn.Module):
     def forward(self, image1: torch.Tensor, image2: torch.Tensor,
                 iters: Optional[int] = None, flow_init: Optional[torch.Tensor] = None,
                 test_mode: bool = True, bidirectional: bool = False,
-                return_low: bool = False):
+                return_low: bool = False, converge=None,
+                return_info: bool = False):
         """Run the recurrent refinement.
 
         image1/image2: [B, 3, H, W] BGR in [0,1] (H, W divisible by 8 —
@@ -119,10 +121,24 @@ class RAFT(nn.Module):
         seeds, so a video session can project it into the next pair's
         warm start: ``(up, low)``, or ``(fw, bw, low_fw, low_bw)`` when
         bidirectional.
+
+        converge=Convergence(...) (test_mode only) makes ``iters`` a
+        budget: the loop measures its own update every few iterations
+        (ops.flow_residual) and, once it is within the tolerance, runs one
+        final iteration and stops — see raft_amd.convergence. The result
+        equals the ungated call with ``iters`` set to the executed count,
+        bit for bit. return_info=True (test_mode only) appends the
+        ConvergenceInfo (iterations run, the checks taken) as the last
+        returned element.
         """
         iters = iters if iters is not None else self.cfg.iters
         if iters < 1:
             raise ValueError(f"iters must be >= 1, got {iters}")
+        if (converge is not None or return_info) and not test_mode:
+            raise ValueError("converge / return_info need test_mode=True")
+        if converge is not None and not isinstance(converge, Convergence):
+            raise ValueError(f"converge must be a Convergence or None, got "
+                             f"{type(converge).__name__}")
         if return_low and not test_mode:
             raise ValueError("return_low=True needs test_mode=True")
         if bidirectional:
@@ -143,7 +159,8 @@ class RAFT(nn.Module):
             if fused.can_fuse(self, image1):
                 return fused.get_fused(self).run(image1, image2, iters,
                                                  flow_init, bidirectional,
-                                                 return_low)
+                                                 return_low, converge,
+                                                 return_info)
 
         img1 = self.preprocess(image1)
         img2 = self.preprocess(image2)
@@ -177,6 +194,17 @@ class RAFT(nn.Module):
 
         flow_predictions: List[torch.Tensor] = []
         up_mask = None
+        if converge is not None:
+            # the gated loop is a path of its own (test mode only): the
+            # ungated loop below, training included, is not touched by it
+            coords1, up_mask, info = self._gated_loop(
+                pyramid, net, inp, coords0, coords1, iters, converge,
+                image1.is_cuda)
+            low = coords1 - coords0
+            return self._pack(self._upsample(low, up_mask), low,
+                              image1.shape[0], bidirectional, return_low,
+                              info if return_info else None)
+
         for _ in range(iters):
             coords1 = coords1.detach()        # RAFT.py:93
             corr = ops.corr_lookup(pyramid,
@@ -196,12 +224,50 @@ class RAFT(nn.Module):
             return flow_predictions
         low = coords1 - coords0
         up = self._upsample(low, up_mask)
-        if bidirectional:
-            B = image1.shape[0]
-            if return_low:
-                return up[:B], up[B:], low[:B], low[B:]
-            return up[:B], up[B:]
-        return (up, low) if return_low else up
+        return self._pack(up, low, image1.shape[0], bidirectional, return_low,
+                          ConvergenceInfo(iters_run=iters) if return_info
+                          else None)
+
+    @staticmethod
+    def _pack(up, low, B, bidirectional, return_low, info):
+        """forward()'s test-mode return value: the flow(s), then the
+        low-resolution flow(s) (return_low), then info (return_info)."""
+        res = (up[:B], up[B:]) if bidirectional else (up,)
+        if return_low:
+            res += (low[:B], low[B:]) if bidirectional else (low,)
+        if info is not None:
+            res += (info,)
+        return res if len(res) > 1 else res[0]
+
+    def _gated_loop(self, pyramid, net, inp, coords0, coords1, budget,
+                    converge, channels_last):
+        """The test-mode refinement loop under a convergence gate
+        (raft_amd.convergence): the iterations of forward()'s loop, with
+        the coords update measured (ops.flow_residual on the planar
+        coords) after the check iterations and one final iteration after
+        convergence. Returns (coords1, up_mask, ConvergenceInfo)."""
+        gate = Gate(converge, budget, coords1.shape[2] * coords1.shape[3])
+        up_mask = None
+        last = False                # converged: this iteration is the final
+        for it in range(1, budget + 1):
+            gate.info.iters_run = it
+            prev = coords1 = coords1.detach()
+            corr = ops.corr_lookup(pyramid,
+                                   coords1.permute(0, 2, 3, 1).contiguous(),
+                                   self.cfg.corr_radius)
+            corr = corr.to(net.dtype)
+            flow = (coords1 - coords0).to(net.dtype)
+            if channels_last:
+                flow = flow.contiguous(memory_format=torch.channels_last)
+            net, up_mask, delta_flow = self.update_block(net, inp, corr, flow)
+            coords1 = coords1 + delta_flow.float()
+            if last:
+                break
+            if gate.wants(it):
+                max_sq, above = ops.flow_residual(prev, coords1, gate.thr_sq)
+                last = gate.record(it, max_sq.cpu().numpy(),
+                                   above.cpu().numpy())
+        return coords1, up_mask, gate.info
 
     def _upsample(self, flow: torch.Tensor, up_mask: Optional[torch.Tensor]):
         if self.cfg.small:

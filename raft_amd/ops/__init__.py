@@ -64,4 +64,5 @@ from raft_amd.ops import torch_ref  # noqa: E402,F401
 from raft_amd.ops.functional import (  # noqa: E402,F401
     corr_volume, corr_pyramid, corr_lookup, gru_gates, convex_upsample,
     upflow8, fb_consistency, forward_project, interpolate_frame,
+    flow_residual, flow_residual_raw,
 )

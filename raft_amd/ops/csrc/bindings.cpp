@@ -70,6 +70,8 @@ void launch_fb_consistency(const void*, const void*, unsigned char*, float*,
                            hipStream_t);
 int launch_flow_project(const float*, unsigned long long*, float*,
                         unsigned char*, int, int, int, int, hipStream_t);
+int launch_flow_residual(const float*, const float*, int*, int, int,
+                         long long, long long, long long, float, hipStream_t);
 int launch_frame_interp(const float*, const float*, const float*,
                         const float*, const unsigned char*,
                         const unsigned char*, unsigned long long*, float*,
@@ -472,6 +474,77 @@ std::vector<at::Tensor> forward_project(at::Tensor flow, int64_t direction) {
     TORCH_CHECK(err == 0, "forward_project: ",
                 hipGetErrorString((hipError_t)err));
     return {out, holes};
+}
+
+// flow_residual reads a logical [B,2,H,W] pair in place when both tensors
+// share their strides and the H*W cells of a sample sit at one stride.
+// The stride of a size-1 dim carries no meaning (contiguous() may leave
+// any value there), so it is neither tested nor used.
+bool residual_one_cell_stride(const at::Tensor& t) {
+    const int64_t H = t.size(2), W = t.size(3);
+    return H == 1 || W == 1 || t.stride(2) == W * t.stride(3);
+}
+
+int64_t residual_cell_stride(const at::Tensor& t) {
+    return t.size(3) == 1 ? t.stride(2) : t.stride(3);
+}
+
+bool residual_same_layout(const at::Tensor& a, const at::Tensor& b) {
+    // strides compared where they are used: sample, component, cell
+    return (a.size(0) == 1 || a.stride(0) == b.stride(0)) &&
+           a.stride(1) == b.stride(1) &&
+           (a.size(2) * a.size(3) == 1 ||
+            residual_cell_stride(a) == residual_cell_stride(b));
+}
+
+bool flow_residual_in_place(at::Tensor prev, at::Tensor nxt) {
+    // True when flow_residual would read this pair without a copy.
+    TORCH_CHECK(prev.dim() == 4 && prev.size(1) == 2,
+                "prev must be [B,2,H,W]");
+    TORCH_CHECK(prev.sizes() == nxt.sizes(), "prev and nxt differ in shape");
+    return residual_same_layout(prev, nxt) &&
+           residual_one_cell_stride(prev) && residual_one_cell_stride(nxt);
+}
+
+at::Tensor flow_residual(at::Tensor prev, at::Tensor nxt, double thr_sq,
+                         c10::optional<at::Tensor> out) {
+    // prev/nxt: logical [B,2,H,W] fp32 with equal strides whose cells sit
+    // at one stride (planar NCHW, or the permuted view of an interleaved
+    // [B,H,W,2] tensor): read in place. Returns the [B,2] int32 result —
+    // column 0 the bits of max_sq, column 1 the count of cells above
+    // thr_sq — written into `out` when given. Memset + one kernel on the
+    // current stream: capturable, no host sync.
+    CHECK_DEV(prev); CHECK_DEV(nxt);
+    TORCH_CHECK(prev.dim() == 4 && prev.size(1) == 2,
+                "prev must be [B,2,H,W]");
+    TORCH_CHECK(prev.sizes() == nxt.sizes(), "prev and nxt differ in shape");
+    TORCH_CHECK(prev.scalar_type() == at::kFloat &&
+                nxt.scalar_type() == at::kFloat, "prev and nxt must be fp32");
+    const int64_t B = prev.size(0), H = prev.size(2), W = prev.size(3);
+    TORCH_CHECK(B <= 65535, "batch must fit the grid's y dimension");
+    TORCH_CHECK(H * W < (int64_t(1) << 31), "H*W must be below 2^31");
+    if (!flow_residual_in_place(prev, nxt)) {
+        prev = prev.contiguous();
+        nxt = nxt.contiguous();
+    }
+    at::Tensor res;
+    if (out.has_value()) {
+        res = *out;
+        CHECK_DEV(res); CHECK_CONT(res);
+        TORCH_CHECK(res.scalar_type() == at::kInt && res.dim() == 2 &&
+                    res.size(0) == B && res.size(1) == 2,
+                    "out must be [B,2] int32");
+    } else {
+        res = at::empty({B, 2}, prev.options().dtype(at::kInt));
+    }
+    const int err = launch_flow_residual(
+        prev.data_ptr<float>(), nxt.data_ptr<float>(), res.data_ptr<int>(),
+        (int)B, (int)(H * W), prev.stride(0), residual_cell_stride(prev),
+        prev.stride(1),
+        (float)thr_sq, current_stream());
+    TORCH_CHECK(err == 0, "flow_residual: ",
+                hipGetErrorString((hipError_t)err));
+    return res;
 }
 
 std::vector<at::Tensor> interpolate_frame(at::Tensor im0, at::Tensor im1,
@@ -1047,6 +1120,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "deterministic forward projection of a flow field -> "
           "(projected, holes)",
           py::arg("flow"), py::arg("direction") = 1);
+    m.def("flow_residual", &flow_residual,
+          "per-sample (max squared coords update bits, cells above thr_sq) "
+          "-> [B,2] int32",
+          py::arg("prev"), py::arg("nxt"), py::arg("thr_sq"),
+          py::arg("out") = py::none());
+    m.def("flow_residual_in_place", &flow_residual_in_place,
+          "whether flow_residual reads this pair without a copy",
+          py::arg("prev"), py::arg("nxt"));
     m.def("interpolate_frame", &interpolate_frame,
           "frame at time t from a bidirectional flow pair -> "
           "(frame, flow_t0, flow_t1, cover)",

@@ -297,6 +297,41 @@ def forward_project(flow: torch.Tensor, direction: int = 1):
     return torch_ref.forward_project(flow.detach(), direction)
 
 
+def flow_residual_raw(prev: torch.Tensor, nxt: torch.Tensor, thr_sq: float,
+                      out=None) -> torch.Tensor:
+    """The HIP op behind ``flow_residual`` without the unpacking: a [B,2]
+    int32 device tensor, column 0 the fp32 bits of max_sq, column 1 the
+    count of cells above ``thr_sq``. prev/nxt are logical [B,2,H,W] fp32
+    views — planar, or the permuted view of interleaved [B,H,W,2] coords —
+    read in place. One memset and one kernel on the current stream, so a
+    loop can launch it between iterations and read the result later.
+    ``out`` reuses a result tensor."""
+    from raft_amd.ops import require_hip
+    return require_hip().flow_residual(prev.detach(), nxt.detach(),
+                                       float(thr_sq), out)
+
+
+def flow_residual(prev: torch.Tensor, nxt: torch.Tensor, thr_sq: float):
+    """Per-sample size of a coords update: ``(max_sq [B] fp32, above [B]
+    int64)`` — the largest squared displacement between ``prev`` and
+    ``nxt`` ([B,2,H,W] fp32) and the number of cells whose squared
+    displacement is not ``<= thr_sq``. See torch_ref.flow_residual for the
+    definition; the GPU kernel matches it bit for bit, is stream-ordered
+    (no host sync) and graph-capturable. No autograd. A CUDA tensor without
+    the built extension is an error, not a fall-back to the oracle;
+    ``RAFT_AMD_FORCE_TORCH=1`` selects the oracle explicitly."""
+    if _use_hip(prev):
+        if prev.dim() != 4 or prev.shape[1] != 2 or prev.shape != nxt.shape:
+            raise ValueError(f"prev and nxt must both be [B,2,H,W], got "
+                             f"{tuple(prev.shape)} and {tuple(nxt.shape)}")
+        if prev.dtype != torch.float32 or nxt.dtype != torch.float32:
+            prev, nxt = prev.float(), nxt.float()
+        res = flow_residual_raw(prev, nxt, thr_sq)
+        return (res[:, 0].contiguous().view(torch.float32),
+                res[:, 1].to(torch.int64))
+    return torch_ref.flow_residual(prev, nxt, thr_sq)
+
+
 def interpolate_frame(im0: torch.Tensor, im1: torch.Tensor,
                       flow_fw: torch.Tensor, flow_bw: torch.Tensor,
                       occ_fw: torch.Tensor, occ_bw: torch.Tensor, t: float):

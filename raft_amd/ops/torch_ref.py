@@ -344,6 +344,37 @@ def forward_project(flow: torch.Tensor, direction: int = 1):
     return out, ~cov.unsqueeze(1)
 
 
+def flow_residual(prev: torch.Tensor, nxt: torch.Tensor, thr_sq: float):
+    """Size of one refinement update — what the convergence gate measures.
+    This definition is the contract: the HIP kernel
+    (csrc/flow_residual.hip) matches it bit for bit.
+
+    prev, nxt: [B,2,H,W] fp32, the 1/8-grid coordinates before and after
+    one iteration. Returns ``(max_sq [B] fp32, above [B] int64)``.
+
+    Per cell dx = nxt.x - prev.x, dy = nxt.y - prev.y and d2 = dx*dx +
+    dy*dy, all fp32, each operation rounded on its own (no FMA).
+    ``max_sq[b]`` is the maximum of d2 over the cells of sample b: NaN (any
+    payload) if any cell is NaN, +inf orders normally. ``above[b]`` counts
+    the cells with ``not (d2 <= thr_sq)`` (thr_sq rounded to fp32): a cell
+    at exactly thr_sq is not above, a NaN cell is.
+    """
+    if prev.dim() != 4 or prev.shape[1] != 2 or prev.shape != nxt.shape:
+        raise ValueError(f"prev and nxt must both be [B,2,H,W], got "
+                         f"{tuple(prev.shape)} and {tuple(nxt.shape)}")
+    B = prev.shape[0]
+    d = nxt.detach().float() - prev.detach().float()
+    dx, dy = d[:, 0], d[:, 1]
+    xx = dx * dx
+    yy = dy * dy
+    d2 = (xx + yy).reshape(B, -1)
+    thr = torch.tensor(thr_sq, dtype=torch.float32, device=d2.device)
+    above = (~(d2 <= thr)).sum(dim=1)
+    if d2.shape[1] == 0:
+        return d2.new_zeros(B), above
+    return d2.max(dim=1).values, above       # torch's max propagates NaN
+
+
 def _check_interp_args(im0, im1, flow_fw, flow_bw, occ_fw, occ_bw, t):
     """Argument contract of interpolate_frame; returns t as a float."""
     try:

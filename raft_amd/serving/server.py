@@ -90,7 +90,22 @@ def create_app(model=None, iters: Optional[int] = None,
     infer_lock = threading.Lock()
     max_body = int(os.environ.get("RAFT_AMD_MAX_BODY_MB", "256")) * 1024 * 1024
 
-    def _run_flow(body: bytes, iters_req: Optional[int]) -> np.ndarray:
+    def _gate(tol, check_every, min_iters):
+        """Query parameters -> Convergence or None; ValueError (-> 400)
+        on bad values."""
+        if tol is None:
+            if check_every is not None or min_iters is not None:
+                raise ValueError("check_every / min_iters need tol")
+            return None
+        from raft_amd import Convergence
+        kw = {}
+        if check_every is not None:
+            kw["every"] = check_every
+        if min_iters is not None:
+            kw["min_iters"] = min_iters
+        return Convergence(tol=tol, **kw)
+
+    def _run_flow(body: bytes, iters_req: Optional[int], converge=None):
         (n1,) = struct.unpack_from("<I", body, 0)
         im1 = _decode_image_bytes(body[4:4 + n1])
         im2 = _decode_image_bytes(body[4 + n1:])
@@ -99,10 +114,12 @@ def create_app(model=None, iters: Optional[int] = None,
                 f"frame shapes differ: {tuple(im1.shape[2:])} vs "
                 f"{tuple(im2.shape[2:])}")
         with infer_lock:
-            out = engine(im1, im2, iters=iters_req)
-        return out[0].float().permute(1, 2, 0).cpu().numpy()
+            out = engine(im1, im2, iters=iters_req, converge=converge)
+            ran = engine.last_info.iters_run
+        return out[0].float().permute(1, 2, 0).cpu().numpy(), ran
 
-    def _run_flow_batch(body: bytes, iters_req: Optional[int]) -> bytes:
+    def _run_flow_batch(body: bytes, iters_req: Optional[int],
+                        converge=None):
         from concurrent.futures import ThreadPoolExecutor
         from raft_amd.engine.inference import run_mixed_batch
         (n_pairs,) = struct.unpack_from("<I", body, 0)
@@ -127,10 +144,12 @@ def create_app(model=None, iters: Optional[int] = None,
             if a.shape != b.shape:
                 raise ValueError(f"pair {i}: frame shapes differ")
         with infer_lock:
-            flows = run_mixed_batch(engine, pairs, iters=iters_req)
+            flows, ran = run_mixed_batch(engine, pairs, iters=iters_req,
+                                         converge=converge,
+                                         return_iters=True)
         return b"".join(
             _flo_bytes(f[0].float().permute(1, 2, 0).cpu().numpy())
-            for f in flows)
+            for f in flows), ran
 
     app = FastAPI(title="raft_amd flow service")
     # per-app registry: repeated create_app() in one process (tests,
@@ -142,6 +161,11 @@ def create_app(model=None, iters: Optional[int] = None,
                              registry=registry)
     latency = Histogram("raft_request_seconds", "end-to-end request latency",
                         registry=registry)
+    iters_run = Histogram("raft_iters_run",
+                          "refinement iterations executed per pair",
+                          buckets=(1, 2, 3, 4, 6, 8, 12, 16, 20, 24, 32, 48,
+                                   64),
+                          registry=registry)
 
     @app.get("/healthz")
     def healthz():
@@ -155,9 +179,15 @@ def create_app(model=None, iters: Optional[int] = None,
 
     @app.post("/flow")
     async def flow(request: Request, fmt: str = "flo",
-                   iters: Optional[int] = None):
+                   iters: Optional[int] = None,
+                   tol: Optional[float] = None,
+                   check_every: Optional[int] = None,
+                   min_iters: Optional[int] = None):
         """Body framing (no multipart dependency):
-        [uint32-le len(img1)] [img1 bytes] [img2 bytes] (PNG or JPEG)."""
+        [uint32-le len(img1)] [img1 bytes] [img2 bytes] (PNG or JPEG).
+        tol (full-resolution pixels) gates the refinement loop, checked
+        every check_every iterations from min_iters on; the executed count
+        comes back in X-Raft-Iters."""
         t0 = time.perf_counter()
         if fmt not in ("flo", "color"):
             request_errors.inc()
@@ -168,8 +198,9 @@ def create_app(model=None, iters: Optional[int] = None,
             if len(body) > max_body:
                 request_errors.inc()
                 return Response("payload too large", status_code=413)
-            flow_np = await asyncio.get_event_loop().run_in_executor(
-                None, _run_flow, body, iters)
+            converge = _gate(tol, check_every, min_iters)
+            flow_np, ran = await asyncio.get_event_loop().run_in_executor(
+                None, _run_flow, body, iters, converge)
             if fmt == "color":
                 from raft_amd.utils.flow_viz import flow_to_color
                 from raft_amd.data.imageio import encode_png
@@ -181,7 +212,9 @@ def create_app(model=None, iters: Optional[int] = None,
                 media = "application/octet-stream"
             requests_total.inc()
             latency.observe(time.perf_counter() - t0)
-            return Response(payload, media_type=media)
+            iters_run.observe(ran)
+            return Response(payload, media_type=media,
+                            headers={"X-Raft-Iters": str(ran)})
         except (ValueError, struct.error, IndexError) as e:
             request_errors.inc()   # malformed body/image: client error
             return Response(f"bad request: {e}", status_code=400)
@@ -190,24 +223,34 @@ def create_app(model=None, iters: Optional[int] = None,
             raise
 
     @app.post("/flow_batch")
-    async def flow_batch(request: Request, iters: Optional[int] = None):
+    async def flow_batch(request: Request, iters: Optional[int] = None,
+                         tol: Optional[float] = None,
+                         check_every: Optional[int] = None,
+                         min_iters: Optional[int] = None):
         """Batched flow with per-pair dynamic shapes. Body framing:
         [uint32-le n_pairs] then per pair
         [uint32 len(png1)][png1][uint32 len(png2)][png2].
         Same-shape pairs are grouped into one engine call
         (run_mixed_batch — BASELINE config 5 semantics); the response is
-        the concatenation of one .flo record per pair, input order."""
+        the concatenation of one .flo record per pair, input order.
+        tol / check_every / min_iters gate each shape group on its own;
+        X-Raft-Iters lists the executed count of every pair."""
         t0 = time.perf_counter()
         try:
             body = await request.body()
             if len(body) > max_body:
                 request_errors.inc()
                 return Response("payload too large", status_code=413)
-            payload = await asyncio.get_event_loop().run_in_executor(
-                None, _run_flow_batch, body, iters)
+            converge = _gate(tol, check_every, min_iters)
+            payload, ran = await asyncio.get_event_loop().run_in_executor(
+                None, _run_flow_batch, body, iters, converge)
             requests_total.inc()
             latency.observe(time.perf_counter() - t0)
-            return Response(payload, media_type="application/octet-stream")
+            for n in ran:
+                iters_run.observe(n)
+            return Response(payload, media_type="application/octet-stream",
+                            headers={"X-Raft-Iters":
+                                     ",".join(str(n) for n in ran)})
         except (ValueError, struct.error, IndexError) as e:
             request_errors.inc()
             return Response(f"bad request: {e}", status_code=400)
