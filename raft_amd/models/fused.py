@@ -5,11 +5,13 @@ Runs the whole RAFT refinement loop on the hand-written gfx950 kernels
 tensors throughout:
 
   encoders (PyTorch/MIOpen, channels-last)  ->  bf16 NT-GEMM corr volume
-  -> bf16 pooled pyramid -> per iteration: NHWC lookup (channel-padded) ->
-  fused motion encoder (5 fconvs writing into the reusable GRU input
-  buffer) -> fused SepConvGRU (2 fconv pairs per direction with the gate
-  math in the epilogue) -> fused flow head + mask head -> coords update
-  -> final convex upsample.
+  -> bf16 pooled pyramid -> per iteration: NHWC lookup fused with the
+  motion encoder's first corr conv (the taps never leave LDS) -> rest of
+  the motion encoder (4 fconvs, the flow branch on a second stream from
+  the start of the iteration, writing into the reusable GRU input buffer)
+  -> fused SepConvGRU (2 fconv pairs per direction with the gate math in
+  the epilogue) -> fused flow head + mask head -> coords update, which
+  also writes the next iteration's flow input -> final convex upsample.
 
 This path is inference-only (no autograd) and numerics-matched to the
 eager model (tests/test_fused.py compares against the fp32 golden path).
@@ -143,15 +145,98 @@ class _GruDirFP8:
                                    self.q_aw, self.kh, self.kw, z, h)
 
 
-class FusedBasicUpdate:
+def pack_smallc(wp: torch.Tensor) -> torch.Tensor:
+    """[taps, N, C] packed weights -> the [N, 128] image fconv_smallc_packed
+    reads its B fragments from: k = tap*C + c, zero tail."""
+    taps, N, C = wp.shape
+    img = wp.new_zeros(N, 128)
+    img[:, :taps * C] = wp.permute(1, 0, 2).reshape(N, taps * C)
+    return img.contiguous()
+
+
+class _MotionFront:
+    """The front of the motion encoder shared by both update blocks: the
+    corr branch (lookup -> convc1 [-> convc2]) and the flow branch (convf1
+    -> convf2), independent until ``conv`` and each latency-bound, so they
+    run on two streams.
+
+    early_fork: the flow channels of x_buf are written by the delta-flow
+    kernel of the previous iteration (by ops.flow_slice at loop entry), so
+    both branches depend on coords1 alone and the fork comes first; off,
+    the lookup writes them and the flow branch follows it.
+    f1_packed: convf1 on fconv_smallc_packed (weights packed once, here)."""
+
+    def _init_front(self, enc, early_fork: bool, f1_packed: bool):
+        self.f1 = _FC(enc.convf1)                    # Cin=2: small-K direct
+        self.f2 = _FC(enc.convf2)
+        self.early_fork = early_fork
+        taps, N, C = self.f1.wp.shape
+        self.f1_pk = None
+        if (f1_packed and C <= 4 and taps * C <= 128 and N % 16 == 0
+                and N <= 128 and self.f1.kh <= 9 and self.f1.kw <= 9):
+            self.f1_pk = pack_smallc(self.f1.wp)
+        self.side_stream = None                      # set by FusedRaft.run
+        self._ev_fork = torch.cuda.Event()
+        self._ev_join = torch.cuda.Event()
+
+    def _flow_branch(self, hip, x_buf, off):
+        f1 = self.f1
+        if self.f1_pk is not None:
+            flo1 = hip.fconv_smallc_packed(x_buf, self.f1_pk, f1.bias, f1.kh,
+                                           f1.kw, ACT_RELU, off, 2)
+        else:
+            flo1 = hip.fconv_smallk(x_buf, f1.wp, f1.bias, f1.kh, f1.kw,
+                                    ACT_RELU, off, 2, 1)
+        return self.f2(hip, flo1)
+
+    def _front(self, hip, x_buf, off, corr_pad, lookup):
+        """(cor, flo) of one iteration. lookup: None (corr_pad is the
+        lookup's output and x_buf holds the flow) or a callable launching
+        the lookup part, returning (tensor, whether convc1 is applied)."""
+        def head():
+            return lookup() if lookup is not None else (corr_pad, False)
+
+        def tail(t, is_c1):
+            c = t if is_c1 else self.c1(hip, t)
+            c2 = getattr(self, "c2", None)
+            return c2(hip, c) if c2 is not None else c
+
+        side = self.side_stream
+        if side is None or torch.cuda.is_current_stream_capturing():
+            cor = tail(*head())
+            return cor, self._flow_branch(hip, x_buf, off)
+        early = self.early_fork and lookup is not None
+        cur = torch.cuda.current_stream()
+        t = None if early else head()
+        self._ev_fork.record(cur)
+        side.wait_event(self._ev_fork)
+        with torch.cuda.stream(side):
+            flo = self._flow_branch(hip, x_buf, off)
+            self._ev_join.record(side)
+        cor = tail(*(head() if early else t))
+        cur.wait_event(self._ev_join)
+        flo.record_stream(cur)
+        return cor, flo
+
+    def _dflow(self, hip, h1, coords1, x_buf, off):
+        """coords1 + delta-flow; with the early fork also the flow slice
+        of x_buf the next iteration reads."""
+        if self.early_fork:
+            return hip.fconv_dflow_coords(h1, self.fh2.wp, self.fh2.bias,
+                                          coords1, 3, 3, x_buf, off)
+        return hip.fconv_dflow_coords(h1, self.fh2.wp, self.fh2.bias,
+                                      coords1, 3, 3)
+
+
+class FusedBasicUpdate(_MotionFront):
     """Packed raft-things update block (motion enc + SepConvGRU + heads)."""
 
-    def __init__(self, ub, corr_cpad: int, ctx_dim: int, hoist: bool = False):
+    def __init__(self, ub, corr_cpad: int, ctx_dim: int, hoist: bool = False,
+                 early_fork: bool = False, f1_packed: bool = False):
         enc = ub.encoder
         self.c1 = _FC(enc.convc1, pad_cin=corr_cpad)
         self.c2 = _FC(enc.convc2)
-        self.f1 = _FC(enc.convf1)                    # Cin=2: small-K direct
-        self.f2 = _FC(enc.convf2)
+        self._init_front(enc, early_fork, f1_packed)
         self.cv = _FC(enc.conv)                      # in: [cor(192)|flo(64)]
         import os as _os
         hd = ub.gru.convz1.weight.shape[0]
@@ -181,9 +266,6 @@ class FusedBasicUpdate:
         self.fh2 = _FC(ub.flow_head.conv2)
         self.m2 = _FC(ub.mask[2], scale=0.25)        # fold the 0.25 scale
         self.ctx_dim = ctx_dim
-        self.side_stream = None                      # set by FusedRaft.run
-        self._ev_fork = torch.cuda.Event()
-        self._ev_join = torch.cuda.Event()
 
     def precompute(self, hip, x_buf):
         """The loop-invariant context terms of the GRU convs (one fp32
@@ -194,33 +276,12 @@ class FusedBasicUpdate:
                 self.gru2.precompute(hip, x_buf))
 
     def __call__(self, hip, net, x_buf, corr_pad, coords1, final=True,
-                 pre=None):
-        # motion encoder (model_utils.py:110-119). The flow channels of
-        # x_buf were already written by the lookup kernel (fused flow out).
-        # The corr branch (c1->c2) and flow branch (f1->f2) are
-        # independent until cv and each is latency-bound, so they run on
-        # two streams (fork after the lookup, join before cv).
+                 pre=None, lookup=None):
+        # motion encoder (model_utils.py:110-119): corr branch (c1->c2) and
+        # flow branch (f1->f2) on two streams, joined before cv — see
+        # _MotionFront
         ctx = self.ctx_dim
-        side = self.side_stream
-        if side is not None and not torch.cuda.is_current_stream_capturing():
-            cur = torch.cuda.current_stream()
-            self._ev_fork.record(cur)
-            side.wait_event(self._ev_fork)
-            with torch.cuda.stream(side):
-                flo1 = hip.fconv_smallk(x_buf, self.f1.wp, self.f1.bias,
-                                        self.f1.kh, self.f1.kw, ACT_RELU,
-                                        ctx + 126, 2, 1)
-                flo = self.f2(hip, flo1)
-                self._ev_join.record(side)
-            cor = self.c2(hip, self.c1(hip, corr_pad))
-            cur.wait_event(self._ev_join)
-            flo.record_stream(cur)
-        else:
-            cor = self.c2(hip, self.c1(hip, corr_pad))
-            flo1 = hip.fconv_smallk(x_buf, self.f1.wp, self.f1.bias,
-                                    self.f1.kh, self.f1.kw, ACT_RELU,
-                                    ctx + 126, 2, 1)
-            flo = self.f2(hip, flo1)
+        cor, flo = self._front(hip, x_buf, ctx + 126, corr_pad, lookup)
         self.cv(hip, cor, flo, ACT_RELU, out=x_buf, n_off=ctx)   # 126 ch
         # SepConvGRU (model_utils.py:138-156)
         if self.fp8_gru:
@@ -243,28 +304,26 @@ class FusedBasicUpdate:
             # performs on the reference's fetched graph), so run the
             # flow-head 3x3 alone instead of the merged N=512 conv
             h1 = self.fh1(hip, net)
-            coords_new = hip.fconv_dflow_coords(h1, self.fh2.wp,
-                                                self.fh2.bias, coords1, 3, 3)
+            coords_new = self._dflow(hip, h1, coords1, x_buf, ctx + 126)
             return net, None, coords_new
         # final iteration — heads: one merged 3x3 conv (flow_head.conv1 +
         # mask[0] stacked along N); mask from a strided slice; the
         # delta-flow final conv also applies coords1 += dflow in-kernel
         hbuf = hip.fconv_plain(net, None, self.heads_w, self.heads_b, 3, 3,
                                ACT_RELU, None, 0, 0, 0, -1, -1, 1, None)
-        coords_new = hip.fconv_dflow_coords(hbuf, self.fh2.wp,
-                                            self.fh2.bias, coords1, 3, 3)
+        coords_new = self._dflow(hip, hbuf, coords1, x_buf, ctx + 126)
         mask = self.m2(hip, hbuf, act=ACT_NONE, in1_off=256, in1_len=256)
         return net, mask, coords_new
 
 
-class FusedSmallUpdate:
+class FusedSmallUpdate(_MotionFront):
     """Packed raft-small update block (motion enc + ConvGRU, no mask)."""
 
-    def __init__(self, ub, corr_cpad: int, ctx_dim: int, hoist: bool = False):
+    def __init__(self, ub, corr_cpad: int, ctx_dim: int, hoist: bool = False,
+                 early_fork: bool = False, f1_packed: bool = False):
         enc = ub.encoder
         self.c1 = _FC(enc.convc1, pad_cin=corr_cpad)
-        self.f1 = _FC(enc.convf1)                    # Cin=2: small-K direct
-        self.f2 = _FC(enc.convf2)
+        self._init_front(enc, early_fork, f1_packed)
         self.cv = _FC(enc.conv)                      # in: [cor(96)|flo(32)]
         self.hoist = hoist
         self.gru = _GruDir(ub.gru.convz, ub.gru.convr, ub.gru.convq,
@@ -272,42 +331,19 @@ class FusedSmallUpdate:
         self.fh1 = _FC(ub.flow_head.conv1)
         self.fh2 = _FC(ub.flow_head.conv2)
         self.ctx_dim = ctx_dim
-        self.side_stream = None                      # set by FusedRaft.run
-        self._ev_fork = torch.cuda.Event()
-        self._ev_join = torch.cuda.Event()
         # x = [inp(ctx) | motion(80) | flow(2)]; motion encoder out = 80
 
     def precompute(self, hip, x_buf):
         return self.gru.precompute(hip, x_buf) if self.hoist else None
 
     def __call__(self, hip, net, x_buf, corr_pad, coords1, final=True,
-                 pre=None):
+                 pre=None, lookup=None):
         ctx = self.ctx_dim
-        side = self.side_stream
-        if side is not None and not torch.cuda.is_current_stream_capturing():
-            cur = torch.cuda.current_stream()
-            self._ev_fork.record(cur)
-            side.wait_event(self._ev_fork)
-            with torch.cuda.stream(side):
-                flo1 = hip.fconv_smallk(x_buf, self.f1.wp, self.f1.bias,
-                                        self.f1.kh, self.f1.kw, ACT_RELU,
-                                        ctx + 80, 2, 1)
-                flo = self.f2(hip, flo1)
-                self._ev_join.record(side)
-            cor = self.c1(hip, corr_pad)
-            cur.wait_event(self._ev_join)
-            flo.record_stream(cur)
-        else:
-            cor = self.c1(hip, corr_pad)
-            flo1 = hip.fconv_smallk(x_buf, self.f1.wp, self.f1.bias,
-                                    self.f1.kh, self.f1.kw, ACT_RELU,
-                                    ctx + 80, 2, 1)
-            flo = self.f2(hip, flo1)
+        cor, flo = self._front(hip, x_buf, ctx + 80, corr_pad, lookup)
         self.cv(hip, cor, flo, ACT_RELU, out=x_buf, n_off=ctx)   # 80 ch
         net = self.gru(hip, net, x_buf, pre)
         h1 = self.fh1(hip, net)
-        coords_new = hip.fconv_dflow_coords(h1, self.fh2.wp, self.fh2.bias,
-                                            coords1, 3, 3)
+        coords_new = self._dflow(hip, h1, coords1, x_buf, ctx + 80)
         return net, None, coords_new
 
 
@@ -455,14 +491,38 @@ class FusedRaft:
         # The in-place slice read needs a 16-byte aligned context width.
         hoist = (os.environ.get("RAFT_AMD_GRU_HOIST", "1") != "0"
                  and cfg.context_dim % 8 == 0)
+        # The motion-encoder front (profiles/motion_front.md), each default
+        # 1, 0 = the earlier path, read here like the hoist:
+        # RAFT_AMD_EARLY_FORK: the delta-flow kernel writes the next
+        #   iteration's flow slice, so the flow branch forks before the
+        #   lookup instead of after it;
+        # RAFT_AMD_LOOKUP_CONV: lookup and convc1 as one kernel
+        #   (ops.corr_lookup_conv1x1), no lookup buffer;
+        # RAFT_AMD_CONVF1_PACKED: convf1 on ops.fconv_smallc_packed
+        #   (weights packed once, one block per position tile). Only with
+        #   RAFT_AMD_SMALLC_MFMA at its default: 0 there selects the
+        #   direct kernels behind ops.fconv_smallk.
+        def switch(name):
+            return os.environ.get(name, "1") != "0"
+        early = switch("RAFT_AMD_EARLY_FORK")
+        f1pk = (switch("RAFT_AMD_CONVF1_PACKED")
+                and switch("RAFT_AMD_SMALLC_MFMA"))
         if cfg.small:
             self.update = FusedSmallUpdate(model.update_block, self.corr_cpad,
-                                           cfg.context_dim, hoist)
+                                           cfg.context_dim, hoist, early,
+                                           f1pk)
             self.x_dim = cfg.context_dim + 82
         else:
             self.update = FusedBasicUpdate(model.update_block, self.corr_cpad,
-                                           cfg.context_dim, hoist)
+                                           cfg.context_dim, hoist, early,
+                                           f1pk)
             self.x_dim = cfg.context_dim + 128
+        self.early_fork = early
+        self.convf1_packed = self.update.f1_pk is not None
+        self.lookup_conv = (switch("RAFT_AMD_LOOKUP_CONV")
+                            and self.hip.lookup_conv_serves(
+                                1, self.corr_c, self.corr_cpad,
+                                self.update.c1.wp.shape[1]))
         self.gru_hoist = self.update.hoist
         self.fuse_enc = os.environ.get("RAFT_AMD_EAGER_ENC", "0") != "1"
         if self.fuse_enc:
@@ -488,30 +548,59 @@ class FusedRaft:
         capture-time workspace fallbacks. Returns (upsampled flow, the
         1/8-resolution flow coords1 - coords0 as [B,H8,W8,2] fp32)."""
         hip = self.hip
-        B, H8, W8, _ = coords0.shape
-        corr_buf = torch.zeros(B, H8, W8, self.corr_cpad,
-                               device=net.device, dtype=torch.bfloat16)
+        corr_buf = self._corr_buf(net)
         mask = None
         # the context channels of x_buf never change inside the loop: their
         # share of the GRU pre-activations is computed once, here, so it is
         # part of a captured loop and reads the graph's static x_buf
         pre = self.update.precompute(hip, x_buf)
+        self._enter(x_buf, coords1)
         for it in range(iters):
             net, mask, coords1 = self._iteration(
                 levels, net, x_buf, corr_buf, coords1, pre,
                 final=(it == iters - 1))
         return self._upsample(coords0, coords1, mask)
 
+    def _corr_buf(self, net):
+        """The lookup's output buffer (pad channels zero), or None where
+        the fused lookup -> convc1 kernel makes it unnecessary."""
+        if self.lookup_conv:
+            return None
+        B, H8, W8, _ = net.shape
+        return torch.zeros(B, H8, W8, self.corr_cpad, device=net.device,
+                           dtype=torch.bfloat16)
+
+    def _enter(self, x_buf, coords1):
+        """Loop entry: with the early fork no kernel of the first
+        iteration writes the flow slice of x_buf, so it is written here
+        from the starting coords1 (warm start included)."""
+        if self.early_fork:
+            self.hip.flow_slice(coords1, x_buf, self.x_dim - 2)
+
     def _iteration(self, levels, net, x_buf, corr_buf, coords1, pre, final):
         """One refinement iteration: (net, mask or None, new coords1)."""
-        # lookup writes the taps AND flow = coords1 - grid directly
-        # into the GRU input buffer's flow slice (zero glue kernels)
-        corr_pad = self.hip.corr_lookup_nhwc(
-            list(levels), coords1, self.model.cfg.corr_radius,
-            self.corr_cpad, True, corr_buf, x_buf, self.x_dim - 2,
-            getattr(self, "_vol_scale", None))
-        return self.update(self.hip, net, x_buf, corr_pad, coords1,
-                           final=final, pre=pre)
+        hip, upd = self.hip, self.update
+        radius = self.model.cfg.corr_radius
+        off = self.x_dim - 2
+        vs = getattr(self, "_vol_scale", None)
+        early = self.early_fork
+
+        def lookup():
+            if corr_buf is None:
+                # lookup -> convc1 in one kernel; it writes no flow
+                if not early:
+                    hip.flow_slice(coords1, x_buf, off)
+                return hip.corr_lookup_conv1x1(
+                    list(levels), coords1, radius, upd.c1.wp, upd.c1.bias,
+                    ACT_RELU, vs), True
+            # without the early fork the lookup also writes flow =
+            # coords1 - grid into the GRU input buffer's flow slice
+            return hip.corr_lookup_nhwc(
+                list(levels), coords1, radius, self.corr_cpad, True,
+                corr_buf, None if early else x_buf, off, vs), False
+
+        return upd(hip, net, x_buf, None, coords1, final=final, pre=pre,
+                   lookup=lookup)
 
     def _upsample(self, coords0, coords1, mask):
         cfg = self.model.cfg
@@ -807,10 +896,9 @@ class FusedRaft:
         decision, then the final one (merged heads + mask) and the
         upsample — the kernel sequence of _loop with iters = the executed
         count."""
-        B, H8, W8, _ = coords0.shape
-        corr_buf = torch.zeros(B, H8, W8, self.corr_cpad,
-                               device=net.device, dtype=torch.bfloat16)
+        corr_buf = self._corr_buf(net)
         pre = self.update.precompute(self.hip, x_buf)
+        self._enter(x_buf, coords1)
         last = False
         for it in range(1, gate.budget + 1):
             final = last or it == gate.budget
@@ -857,6 +945,7 @@ class FusedRaft:
     def _replay_gated(self, graphs, st, gate):
         step, tail = graphs
         self._set_pre(st)
+        self._enter(st["x_buf"], st["coords1"])
         last = False
         for it in range(1, gate.budget + 1):
             if last or it == gate.budget:
@@ -894,11 +983,9 @@ class FusedRaft:
         (final iteration + upsample)."""
         st = self._static(levels, net, inp, coords0, coords1)
         st["coords_prev"] = coords1.clone()
-        st["corr_buf"] = torch.zeros(net.shape[0], net.shape[1],
-                                     net.shape[2], self.corr_cpad,
-                                     device=net.device,
-                                     dtype=torch.bfloat16)
+        st["corr_buf"] = self._corr_buf(net)
         st["pre"] = self.update.precompute(self.hip, st["x_buf"])
+        self._enter(st["x_buf"], st["coords1"])
         # warm up on a side stream (allocator steady-state before capture)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())

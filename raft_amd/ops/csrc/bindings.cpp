@@ -3,6 +3,7 @@
 // HIP stream. Device code lives in the .hip files; each exposes an
 // extern "C" launcher so this TU needs no cross-TU kernel symbols.
 #include <torch/extension.h>
+#include "lookup_conv_geom.h"
 
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
@@ -102,7 +103,17 @@ void launch_fconv_smallk_nhwc_bf16(const void*, int, int, const void*,
                                    const float*, void*, int, int, int, int,
                                    int, int, int, int, int, hipStream_t);
 void launch_fconv_dflow_coords(const void*, int, int, int, const void*,
-                               const float*, const float*, float*, int, int,
+                               const float*, const float*, float*, void*,
+                               int, int, int, int, int, int, int,
+                               hipStream_t);
+void launch_flow_slice(const float*, void*, int, int, int, int, int,
+                       hipStream_t);
+int launch_corr_lookup_conv1x1(const void* const*, const int*, const int*,
+                               int, const float*, const float*, const void*,
+                               const float*, void*, int, int, int, int, int,
+                               int, int, int, hipStream_t);
+int launch_fconv_smallc_packed(const void*, int, int, const void*,
+                               const float*, void*, int, int, int, int, int,
                                int, int, int, hipStream_t);
 }
 
@@ -1047,19 +1058,140 @@ at::Tensor fconv_smallk(at::Tensor in1, at::Tensor wp,
 }
 
 at::Tensor fconv_dflow_coords(at::Tensor in1, at::Tensor wp, at::Tensor bias,
-                              at::Tensor coords, int64_t kh, int64_t kw) {
+                              at::Tensor coords, int64_t kh, int64_t kw,
+                              c10::optional<at::Tensor> flow_buf,
+                              int64_t flow_off) {
     // delta-flow 3x3 -> 2 head with the coords update fused:
-    // returns coords_new = coords + conv(in1)
+    // returns coords_new = coords + conv(in1). flow_buf: also write
+    // bf16(coords_new - pixel grid) into channels [flow_off, flow_off+2)
+    // of that NHWC buffer (the next iteration's flow input).
     CHECK_DEV(in1); CHECK_CONT(in1); CHECK_CONT(wp); CHECK_CONT(coords);
     const int B = in1.size(0), H = in1.size(1), W = in1.size(2);
     const int Cin = wp.size(2);
     TORCH_CHECK(wp.size(1) == 2 && coords.scalar_type() == at::kFloat);
     auto out = at::empty_like(coords);
+    void* fptr = nullptr;
+    int fstride = 0;
+    if (flow_buf.has_value()) {
+        CHECK_DEV(flow_buf.value());
+        TORCH_CHECK(flow_buf->is_contiguous() && flow_buf->dim() == 4 &&
+                    flow_buf->scalar_type() == at::kBFloat16);
+        TORCH_CHECK(flow_buf->size(0) == B && flow_buf->size(1) == H &&
+                    flow_buf->size(2) == W && flow_off >= 0 &&
+                    flow_off + 2 <= flow_buf->size(3),
+                    "flow_buf does not hold a 2-channel slice at flow_off");
+        fptr = flow_buf->data_ptr();
+        fstride = (int)flow_buf->size(3);
+    }
     launch_fconv_dflow_coords(in1.data_ptr(), Cin, in1.size(3), 0,
                               wp.data_ptr(), bias.data_ptr<float>(),
                               coords.data_ptr<float>(),
-                              out.data_ptr<float>(), B, H, W, (int)kh,
-                              (int)kw, current_stream());
+                              out.data_ptr<float>(), fptr, fstride,
+                              (int)flow_off, B, H, W, (int)kh, (int)kw,
+                              current_stream());
+    return out;
+}
+
+void flow_slice(at::Tensor coords, at::Tensor flow_buf, int64_t flow_off) {
+    // flow_buf[..., flow_off:flow_off+2] = bf16(coords - pixel grid)
+    CHECK_DEV(coords); CHECK_CONT(coords); CHECK_DEV(flow_buf);
+    TORCH_CHECK(coords.scalar_type() == at::kFloat && coords.dim() == 4 &&
+                coords.size(3) == 2);
+    const int B = coords.size(0), H = coords.size(1), W = coords.size(2);
+    TORCH_CHECK(flow_buf.is_contiguous() && flow_buf.dim() == 4 &&
+                flow_buf.scalar_type() == at::kBFloat16);
+    TORCH_CHECK(flow_buf.size(0) == B && flow_buf.size(1) == H &&
+                flow_buf.size(2) == W && flow_off >= 0 &&
+                flow_off + 2 <= flow_buf.size(3),
+                "flow_buf does not hold a 2-channel slice at flow_off");
+    launch_flow_slice(coords.data_ptr<float>(), flow_buf.data_ptr(),
+                      (int)flow_buf.size(3), (int)flow_off, B, H, W,
+                      current_stream());
+}
+
+bool lookup_conv_serves(int64_t positions, int64_t C, int64_t Cs, int64_t N) {
+    return lookup_conv_geom(positions, (int)C, (int)Cs, (int)N, 0).ok != 0;
+}
+
+at::Tensor corr_lookup_conv1x1(std::vector<at::Tensor> levels,
+                               at::Tensor coords, int64_t radius,
+                               at::Tensor wp, c10::optional<at::Tensor> bias,
+                               int64_t act,
+                               c10::optional<at::Tensor> vol_scale) {
+    // act(conv1x1(bf16 lookup(levels, coords))) -> [B, H, W, N] bf16 without
+    // the lookup buffer; wp: packed [1, N, Cs] bf16, zero columns past
+    // L*(2r+1)^2. bf16 or e4m3 (+ vol_scale) volumes.
+    CHECK_DEV(coords); CHECK_CONT(coords); CHECK_DEV(wp); CHECK_CONT(wp);
+    TORCH_CHECK(!levels.empty() && levels.size() <= 4, "1..4 pyramid levels");
+    TORCH_CHECK(coords.scalar_type() == at::kFloat && coords.dim() == 4 &&
+                coords.size(3) == 2);
+    TORCH_CHECK(wp.scalar_type() == at::kBFloat16 && wp.dim() == 3 &&
+                wp.size(0) == 1, "wp must be a packed 1x1 conv [1, N, Cs]");
+    const int B = coords.size(0), H = coords.size(1), W = coords.size(2);
+    const int L = (int)levels.size();
+    const int N = wp.size(1), Cs = wp.size(2);
+    const void* ptrs[4];
+    int hs[4] = {0}, ws[4] = {0};
+    int vol_type = 0;
+    if (levels[0].scalar_type() == at::kBFloat16) vol_type = 1;
+    else if (levels[0].scalar_type() == at::kByte) vol_type = 2;
+    const float* vsp = nullptr;
+    if (vol_type == 2) {
+        TORCH_CHECK(vol_scale.has_value(),
+                    "fp8 volume lookup needs vol_scale");
+        vsp = vol_scale->data_ptr<float>();
+    }
+    for (int i = 0; i < L; ++i) {
+        CHECK_DEV(levels[i]); CHECK_CONT(levels[i]);
+        TORCH_CHECK(levels[i].scalar_type() == levels[0].scalar_type() &&
+                    levels[i].dim() == 4 &&
+                    levels[i].size(0) * levels[i].size(1) ==
+                        (int64_t)B * H * W,
+                    "pyramid level does not match coords");
+        ptrs[i] = levels[i].data_ptr();
+        hs[i] = levels[i].size(2);
+        ws[i] = levels[i].size(3);
+    }
+    const float* bptr = nullptr;
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() == N);
+        bptr = bias->data_ptr<float>();
+    }
+    auto out = at::empty({B, H, W, (int64_t)N},
+                         coords.options().dtype(at::kBFloat16));
+    const int ok = launch_corr_lookup_conv1x1(
+        ptrs, hs, ws, vol_type, vsp, coords.data_ptr<float>(),
+        wp.data_ptr(), bptr, out.data_ptr(), B, H, W, L, (int)radius, Cs, N,
+        (int)act, current_stream());
+    TORCH_CHECK(ok, "corr_lookup_conv1x1: no kernel for this shape or volume "
+                    "type (Cs=", Cs, ", N=", N, ", vol_type=", vol_type,
+                    "); run corr_lookup_nhwc + fconv_plain");
+    return out;
+}
+
+at::Tensor fconv_smallc_packed(at::Tensor in1, at::Tensor wpk,
+                               c10::optional<at::Tensor> bias, int64_t kh,
+                               int64_t kw, int64_t act, int64_t in1_off,
+                               int64_t in1_len) {
+    // fconv_smallk's stride-1 small-C MFMA conv with the weights
+    // pre-packed as [N, 128] (k = tap*C + c, zero tail)
+    CHECK_DEV(in1); CHECK_CONT(in1); CHECK_DEV(wpk); CHECK_CONT(wpk);
+    TORCH_CHECK(in1.scalar_type() == at::kBFloat16 &&
+                wpk.scalar_type() == at::kBFloat16 && wpk.dim() == 2 &&
+                wpk.size(1) == 128, "wpk must be [N, 128] bf16");
+    const int B = in1.size(0), H = in1.size(1), W = in1.size(2);
+    const int stride = in1.size(3);
+    const int C = in1_len > 0 ? (int)in1_len : stride;
+    TORCH_CHECK(in1_off >= 0 && in1_off + C <= stride);
+    const int N = wpk.size(0);
+    const float* bptr = bias.has_value() ? bias->data_ptr<float>() : nullptr;
+    auto out = at::empty({B, H, W, (int64_t)N}, in1.options());
+    const int ok = launch_fconv_smallc_packed(
+        in1.data_ptr(), stride, (int)in1_off, wpk.data_ptr(), bptr,
+        out.data_ptr(), B, H, W, C, N, (int)kh, (int)kw, (int)act,
+        current_stream());
+    TORCH_CHECK(ok, "fconv_smallc_packed: no kernel for C=", C, " N=", N,
+                " ", kh, "x", kw, "; use fconv_smallk");
     return out;
 }
 
@@ -1159,7 +1291,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("inorm_apply", &inorm_apply,
           "instance-norm apply (+relu / +residual-relu)");
     m.def("fconv_dflow_coords", &fconv_dflow_coords,
-          "flow-head final conv fused with the coords update");
+          "flow-head final conv fused with the coords update (+ the next "
+          "iteration's bf16 flow slice into flow_buf)",
+          py::arg("in1"), py::arg("wp"), py::arg("bias"), py::arg("coords"),
+          py::arg("kh"), py::arg("kw"), py::arg("flow_buf") = c10::nullopt,
+          py::arg("flow_off") = 0);
+    m.def("flow_slice", &flow_slice,
+          "flow_buf[..., off:off+2] = bf16(coords - pixel grid)",
+          py::arg("coords"), py::arg("flow_buf"), py::arg("flow_off"));
+    m.def("lookup_conv_serves", &lookup_conv_serves,
+          "whether corr_lookup_conv1x1 has a kernel for this shape",
+          py::arg("positions"), py::arg("C"), py::arg("Cs"), py::arg("N"));
+    m.def("corr_lookup_conv1x1", &corr_lookup_conv1x1,
+          "pyramid lookup fused with the pointwise conv that consumes it",
+          py::arg("levels"), py::arg("coords"), py::arg("radius"),
+          py::arg("wp"), py::arg("bias"), py::arg("act"),
+          py::arg("vol_scale") = c10::nullopt);
+    m.def("fconv_smallc_packed", &fconv_smallc_packed,
+          "small-C MFMA conv, all N per block, host-packed [N,128] weights",
+          py::arg("in1"), py::arg("wpk"), py::arg("bias"), py::arg("kh"),
+          py::arg("kw"), py::arg("act"), py::arg("in1_off") = 0,
+          py::arg("in1_len") = 0);
     m.def("fconv_gru_q", &fconv_gru_q, "GRU candidate conv + state update");
     m.def("fconv_plain_f32", &fconv_plain_f32,
           "NHWC bf16 conv (+bias) with unrounded fp32 output, no activation",

@@ -37,3 +37,11 @@ RAFT_DEV BilinearTap make_tap(float x, float y, int W, int H) {
     t.wd = (1.0f - qx) * (1.0f - qy);
     return t;
 }
+
+// conv epilogue activation: 0 none, 1 relu, 2 sigmoid, 3 tanh
+RAFT_DEV float factivate(float v, int act) {
+    if (act == 1) return fmaxf(v, 0.0f);
+    if (act == 2) return 1.0f / (1.0f + __expf(-v));
+    if (act == 3) return tanhf(v);
+    return v;
+}

@@ -13,6 +13,7 @@
 // window cells (L1-friendly).  Template on the volume dtype (fp32 / bf16).
 
 #include "common.h"
+#include "lookup_conv_geom.h"
 #include <type_traits>
 #include <hip/hip_bf16.h>
 
@@ -326,6 +327,59 @@ RAFT_DEV float lvload<unsigned char>(const unsigned char& v) {
     return __builtin_amdgcn_cvt_f32_fp8((int)v, 0);
 }
 
+// One lookup tap: channel c = lvl*KK + k of query q, as fp32 before the
+// output rounding. The single definition of the tap arithmetic — the
+// lookup kernel and the fused lookup -> conv kernel both evaluate
+// corr_tap_at(corr_tap_col(c), q), so the two produce the same bits. The
+// split lets a caller that keeps c over many queries compute the
+// channel's part (level, window offset, level geometry) once.
+template <typename T>
+struct TapCol {
+    const T* base;     // the level's volume
+    int H2, W2;
+    float inv;         // 1 / 2^lvl
+    float dx, dy;      // window offset of the tap
+};
+
+template <typename T>
+RAFT_DEV TapCol<T> corr_tap_col(const LevelsT& lv, int c, int K, int KK,
+                                int radius) {
+    const int lvl = c / KK;
+    const int k = c - lvl * KK;
+    TapCol<T> t;
+    t.inv = 1.0f / (float)(1 << lvl);
+    t.dx = (float)(k / K - radius);
+    t.dy = (float)(k % K - radius);
+    t.H2 = lv.H[lvl];
+    t.W2 = lv.W[lvl];
+    t.base = (const T*)lv.ptr[lvl];
+    return t;
+}
+
+template <typename T>
+RAFT_DEV float corr_tap_at(const TapCol<T>& tc,
+                           const float* __restrict__ coords, long long q,
+                           float vs) {
+    const float cx = coords[q * 2] * tc.inv + tc.dx;
+    const float cy = coords[q * 2 + 1] * tc.inv + tc.dy;
+
+    const int H2 = tc.H2, W2 = tc.W2;
+    const T* slice = tc.base + q * (size_t)H2 * W2;
+    BilinearTap t = make_tap(cx, cy, W2, H2);
+    const float Ia = lvload(slice[t.y0 * W2 + t.x0]);
+    const float Ib = lvload(slice[t.y1 * W2 + t.x0]);
+    const float Ic = lvload(slice[t.y0 * W2 + t.x1]);
+    const float Id = lvload(slice[t.y1 * W2 + t.x1]);
+    return vs * (t.wa * Ia + t.wb * Ib + t.wc * Ic + t.wd * Id);
+}
+
+template <typename T>
+RAFT_DEV float corr_tap(const LevelsT& lv, const float* __restrict__ coords,
+                        long long q, int c, int K, int KK, int radius,
+                        float vs) {
+    return corr_tap_at(corr_tap_col<T>(lv, c, K, KK, radius), coords, q, vs);
+}
+
 template <typename T, typename OT>
 __global__ void corr_lookup_nhwc_k(
     LevelsT lv, const float* __restrict__ coords,  // [B, H, W, 2]
@@ -343,8 +397,6 @@ __global__ void corr_lookup_nhwc_k(
          idx < total; idx += stride) {
         const int c = (int)(idx % C);
         const long long q = idx / C;               // b*H*W + y*W + x
-        const int lvl = c / KK;
-        const int k = c - lvl * KK;
 
         if (flow_out && c < 2) {
             // fused flow = coords - identity grid (coords0 is the pixel
@@ -355,21 +407,39 @@ __global__ void corr_lookup_nhwc_k(
             flow_out[q * flow_stride + flow_off + c] =
                 (__hip_bfloat16)(coords[q * 2 + c] - base);
         }
-
-        const float inv = 1.0f / (float)(1 << lvl);
-        const float cx = coords[q * 2] * inv + (float)(k / K - radius);
-        const float cy = coords[q * 2 + 1] * inv + (float)(k % K - radius);
-
-        const int H2 = lv.H[lvl], W2 = lv.W[lvl];
-        const T* slice = (const T*)lv.ptr[lvl] + q * (size_t)H2 * W2;
-        BilinearTap t = make_tap(cx, cy, W2, H2);
-        const float Ia = lvload(slice[t.y0 * W2 + t.x0]);
-        const float Ib = lvload(slice[t.y1 * W2 + t.x0]);
-        const float Ic = lvload(slice[t.y0 * W2 + t.x1]);
-        const float Id = lvload(slice[t.y1 * W2 + t.x1]);
         out[q * Cs + c] =
-            (OT)(vs * (t.wa * Ia + t.wb * Ib + t.wc * Ic + t.wd * Id));
+            (OT)corr_tap<T>(lv, coords, q, c, K, KK, radius, vs);
     }
+}
+
+// flow = coords - pixel grid as bf16 into a channel slice of rows of
+// flow_stride elements: what corr_lookup_nhwc_k's flow_out writes, on its
+// own. The fused loop calls it once per loop entry; from then on the
+// delta-flow kernel writes the slice for the next iteration.
+__global__ void flow_slice_k(const float* __restrict__ coords,
+                             __hip_bfloat16* __restrict__ flow_out,
+                             int flow_stride, int flow_off, int H, int W,
+                             long long total) {   // total = B*H*W*2
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+         idx < total; idx += stride) {
+        const int c = (int)(idx & 1);
+        const long long q = idx >> 1;
+        const float base = (c == 0) ? (float)(q % W)
+                                    : (float)((q / W) % H);
+        flow_out[q * flow_stride + flow_off + c] =
+            (__hip_bfloat16)(coords[idx] - base);
+    }
+}
+
+extern "C" void launch_flow_slice(const float* coords, void* flow_out,
+                                  int flow_stride, int flow_off, int B,
+                                  int H, int W, hipStream_t s) {
+    const long long total = (long long)B * H * W * 2;
+    int blocks = (int)min((total + 255) / 256, (long long)2048);
+    hipLaunchKernelGGL(flow_slice_k, dim3(blocks), dim3(256), 0, s, coords,
+                       (__hip_bfloat16*)flow_out, flow_stride, flow_off, H,
+                       W, total);
 }
 
 // vol_type: 0 = fp32, 1 = bf16, 2 = e4m3 (vol_scale dequantizes)
@@ -403,6 +473,171 @@ extern "C" void launch_corr_lookup_nhwc(
     LKCASE(unsigned char, 2, float, false)
     LKCASE(unsigned char, 2, __hip_bfloat16, true)
 #undef LKCASE
+}
+
+// ------------------------------------------- fused lookup -> 1x1 conv
+// out[q, n] = act(sum_c bf16(tap(q, c)) * Wp[n][c] + bias[n]): the lookup
+// and the pointwise conv that consumes it (the motion encoder's convc1)
+// as one kernel, without the [positions, Cs] round trip between them. A
+// pointwise consumer needs no halo, so a block computes the taps of its
+// BM positions straight into LDS as the A operand (rows of Kp = kchunks*32
+// bf16, zero past C — the pad columns of the unfused buffer), and after
+// ONE barrier its waves split the N/16 output-channel tiles: 16x16x32
+// MFMA over the k-chunks in ascending order from a zero accumulator, bias
+// then activation in the epilogue — the order fconv_nhwc_bf16_k uses for
+// a 1x1, so the result is the unfused pair's bit for bit. B fragments come
+// straight from global memory in fragment layout (a lane's 16 bytes at
+// wp[n][k0 + (lane>>4)*8]): the packed weights are L2-resident and shared
+// by every block, and the k-loop needs no barrier. Geometry (tile, grid,
+// LDS) is decided by lookup_conv_geom() in lookup_conv_geom.h.
+template <typename T, int BM, int NW>
+__global__ __launch_bounds__(NW * 64) void corr_lookup_conv1x1_k(
+    LevelsT lv, const float* __restrict__ coords,  // [P, 2]
+    const __hip_bfloat16* __restrict__ wp,         // [N][Cs]
+    const float* __restrict__ bias,                // [N] or null
+    __hip_bfloat16* __restrict__ out,              // [P, N]
+    const float* __restrict__ vol_scale,           // null -> 1.0
+    int num_levels, int radius, int Cs, int N, int act, int kchunks,
+    long long P) {
+    extern __shared__ __hip_bfloat16 lc_sa[];      // [BM][Kp + pad]
+    constexpr int NT = NW * 64;
+    constexpr int MI = BM / 16;
+    constexpr int NJ = 16 / NW;                    // n-tiles per wave (max)
+    const float vs = vol_scale ? *vol_scale : 1.0f;
+    const int K = 2 * radius + 1;
+    const int KK = K * K;
+    const int C = num_levels * KK;
+    const int Kp = kchunks * 32;
+    const int KR = Kp + LCONV_ROW_PAD;
+    const long long q0 = (long long)blockIdx.x * BM;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int kg = lane >> 4;
+    const int l15 = lane & 15;
+    const int ntiles = N >> 4;
+
+    // B fragments of one k-chunk: rows past N (wave-uniform) and columns
+    // past Cs are zero, as the staged weight tiles of the unfused conv
+    auto loadB = [&](int kc, short8* bf) {
+        const int k = kc * 32 + kg * 8;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int nt = wave + j * NW;
+            short8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (nt < ntiles && k < Cs)
+                v = *(const short8*)(wp + (size_t)(nt * 16 + l15) * Cs + k);
+            bf[j] = v;
+        }
+    };
+    short8 bcur[NJ], bnxt[NJ];
+    loadB(0, bcur);          // in flight under the tap phase
+
+    // tap phase: consecutive lanes take consecutive channels of one
+    // query (overlapping window cells), as the lookup kernel does. A
+    // thread keeps its channel over the tile's rows — NT/C rows per pass —
+    // so the channel's part of the tap (integer divisions, level
+    // geometry) is computed once per thread, not once per tap; with fewer
+    // threads than channels it walks the channels instead.
+    const int rpp = NT >= C ? NT / C : 1;          // rows per pass
+    const int r0 = NT >= C ? tid / C : 0;
+    if (r0 < rpp) {
+        for (int c = tid - r0 * C; c < C; c += NT) {
+            const TapCol<T> tc = corr_tap_col<T>(lv, c, K, KK, radius);
+            for (int pos = r0; pos < BM; pos += rpp) {
+                const long long q = q0 + pos;
+                __hip_bfloat16 v = (__hip_bfloat16)0.f;
+                if (q < P)
+                    v = (__hip_bfloat16)corr_tap_at(tc, coords, q, vs);
+                lc_sa[pos * KR + c] = v;
+            }
+        }
+    }
+    // zero columns [C, Kp): the pad channels of the unfused buffer
+    const int padw = Kp - C;
+    for (int e = tid; e < BM * padw; e += NT) {
+        const int pos = e / padw;
+        lc_sa[pos * KR + C + (e - pos * padw)] = (__hip_bfloat16)0.f;
+    }
+    __syncthreads();
+
+    floatx4 acc[MI][NJ];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+    for (int kc = 0; kc < kchunks; ++kc) {
+        if (kc + 1 < kchunks) loadB(kc + 1, bnxt);
+        short8 af[MI];
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+            af[i] = *(const short8*)(lc_sa + (i * 16 + l15) * KR + kc * 32 +
+                                     kg * 8);
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    af[i], bcur[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) bcur[j] = bnxt[j];
+    }
+
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int nt = wave + j * NW;
+        if (nt >= ntiles) continue;
+        const int n = nt * 16 + l15;
+        const float bz = bias ? bias[n] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long long q = q0 + i * 16 + kg * 4 + r;
+                if (q >= P) continue;
+                float v = acc[i][j][r];
+                if (bias) v += bz;
+                out[q * N + n] = (__hip_bfloat16)factivate(v, act);
+            }
+    }
+}
+
+// vol_type: 1 = bf16, 2 = e4m3 (vol_scale dequantizes). Returns 0 when
+// the shape or the volume type is not served: the caller runs the pair.
+extern "C" int launch_corr_lookup_conv1x1(
+    const void* const* level_ptrs, const int* level_h, const int* level_w,
+    int vol_type, const float* vol_scale, const float* coords,
+    const void* wp, const float* bias, void* out, int B, int H, int W,
+    int num_levels, int radius, int Cs, int N, int act, hipStream_t s) {
+    static const int tile = lookup_conv_tile_from_env();
+    const int K = 2 * radius + 1;
+    const long long P = (long long)B * H * W;
+    const LookupConvGeom g =
+        lookup_conv_geom(P, num_levels * K * K, Cs, N, tile);
+    if (!g.ok || (vol_type != 1 && vol_type != 2)) return 0;
+    LevelsT lv{};
+    for (int i = 0; i < num_levels; ++i) {
+        lv.ptr[i] = level_ptrs[i];
+        lv.H[i] = level_h[i];
+        lv.W[i] = level_w[i];
+    }
+#define LCCASE(T, VT, BM_, NW_)                                             \
+    if (vol_type == VT && g.BM == BM_ && g.waves == NW_) {                  \
+        hipLaunchKernelGGL((corr_lookup_conv1x1_k<T, BM_, NW_>),            \
+                           dim3(g.grid), dim3(g.block), g.lds_bytes, s, lv, \
+                           coords, (const __hip_bfloat16*)wp, bias,         \
+                           (__hip_bfloat16*)out, vol_scale, num_levels,     \
+                           radius, Cs, N, act, g.kchunks, P);               \
+        return 1;                                                           \
+    }
+#define LCTILES(T, VT)                                                      \
+    LCCASE(T, VT, 16, 4) LCCASE(T, VT, 16, 8) LCCASE(T, VT, 16, 16)         \
+    LCCASE(T, VT, 32, 4) LCCASE(T, VT, 32, 8) LCCASE(T, VT, 32, 16)
+    LCTILES(__hip_bfloat16, 1)
+    LCTILES(unsigned char, 2)
+#undef LCTILES
+#undef LCCASE
+    return 0;
 }
 
 // backward: scatter into fp32 grad volumes from an NHWC grad_out

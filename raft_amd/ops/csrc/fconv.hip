@@ -71,13 +71,6 @@ RAFT_DEV unsigned fswz(int row, unsigned colbyte) {
            (((unsigned)row & 3u) << 4) ^ ((((unsigned)row >> 2) & 3u) << 6);
 }
 
-RAFT_DEV float factivate(float v, int act) {
-    if (act == 1) return fmaxf(v, 0.0f);
-    if (act == 2) return 1.0f / (1.0f + __expf(-v));
-    if (act == 3) return tanhf(v);
-    return v;
-}
-
 // epilogue modes
 #define EP_PLAIN 0
 #define EP_GRU_ZR 1   // N = 2*hd: [z | r] -> z_buf = sig(z), rh = sig(r)*h
@@ -711,6 +704,10 @@ __global__ __launch_bounds__(256) void fconv_tinyn_k(
     __hip_bfloat16* __restrict__ out,         // [B,H,W,N] (null if coords)
     const float* __restrict__ coords_in,      // fused coords1 += dflow
     float* __restrict__ coords_out,           // (NN == 2 only)
+    // with coords_out: also flow = coords_out - pixel grid as bf16 into a
+    // channel slice of rows of flow_stride elements (the GRU input
+    // buffer's flow channels, as the lookup kernel writes them). Null: off.
+    __hip_bfloat16* __restrict__ flow_out, int flow_stride, int flow_off,
     int H, int W, int kh, int kw, int act, long long ncells) {
     const int lane = threadIdx.x & 63;
     const long long cell = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -749,9 +746,15 @@ __global__ __launch_bounds__(256) void fconv_tinyn_k(
         for (int n = 0; n < NN; ++n) {
             float v = acc[n] + (bias ? bias[n] : 0.0f);
             v = factivate(v, act);
-            if (coords_out)   // fused coords1 = coords1 + delta_flow
-                coords_out[cell * NN + n] = coords_in[cell * NN + n] + v;
-            else
+            if (coords_out) {  // fused coords1 = coords1 + delta_flow
+                const float c = coords_in[cell * NN + n] + v;
+                coords_out[cell * NN + n] = c;
+                if (flow_out) {
+                    const float base = (n == 0) ? (float)x : (float)y;
+                    flow_out[cell * flow_stride + flow_off + n] =
+                        (__hip_bfloat16)(c - base);
+                }
+            } else
                 out[cell * NN + n] = (__hip_bfloat16)v;
         }
     }
@@ -770,6 +773,7 @@ __global__ __launch_bounds__(256) void fconv_tinyn2_k(
     int in_off, const __hip_bfloat16* __restrict__ wp,
     const float* __restrict__ bias, __hip_bfloat16* __restrict__ out,
     const float* __restrict__ coords_in, float* __restrict__ coords_out,
+    __hip_bfloat16* __restrict__ flow_out, int flow_stride, int flow_off,
     int H, int W, int kh, int kw, int act) {
     extern __shared__ __hip_bfloat16 sm2[];
     constexpr int TP = 8;
@@ -829,9 +833,15 @@ __global__ __launch_bounds__(256) void fconv_tinyn2_k(
             for (int n = 0; n < NN; ++n) {
                 float v = acc[n] + (bias ? bias[n] : 0.0f);
                 v = factivate(v, act);
-                if (coords_out)
-                    coords_out[cell * NN + n] = coords_in[cell * NN + n] + v;
-                else
+                if (coords_out) {
+                    const float c = coords_in[cell * NN + n] + v;
+                    coords_out[cell * NN + n] = c;
+                    if (flow_out) {
+                        const float base = (n == 0) ? (float)x : (float)y;
+                        flow_out[cell * flow_stride + flow_off + n] =
+                            (__hip_bfloat16)(c - base);
+                    }
+                } else
                     out[cell * NN + n] = (__hip_bfloat16)v;
             }
         }
@@ -963,8 +973,8 @@ extern "C" void launch_fconv_nhwc_bf16(
         const long long ncells = (long long)B * H * W;
         hipLaunchKernelGGL(fconv_tinyn_k<2>, dim3((unsigned)((ncells + 3) / 4)),
                            blk, 0, s, a.in1, C1, in1_stride, in1_off, a.wp,
-                           bias, a.out, nullptr, nullptr, H, W, kh, kw, act,
-                           ncells);
+                           bias, a.out, nullptr, nullptr, nullptr, 0, 0, H, W,
+                           kh, kw, act, ncells);
         return;
     }
     case FCONV_TINYN2: {
@@ -972,7 +982,8 @@ extern "C" void launch_fconv_nhwc_bf16(
         hipLaunchKernelGGL(fconv_tinyn2_k<2>,
                            dim3((unsigned)(H * ((W + 7) / 8)), 1, (unsigned)B),
                            blk, smem, s, a.in1, C1, in1_stride, in1_off, a.wp,
-                           bias, a.out, nullptr, nullptr, H, W, kh, kw, act);
+                           bias, a.out, nullptr, nullptr, nullptr, 0, 0, H, W,
+                           kh, kw, act);
         return;
     }
     case FCONV_STEM:
@@ -1198,6 +1209,131 @@ extern "C" __global__ __launch_bounds__(256) void fconv_smallc_mfma_k(
     }
 }
 
+// fconv_smallc_mfma_k with one block per 32-position tile computing ALL N
+// output channels, and the weights pre-packed on the host into the [N][128]
+// image its B fragments read (k = tap*C + c, zero tail — packed once: the
+// weights never change). The kernel above runs N/32 blocks per position
+// tile, each re-laying its weight slice into LDS with scalar stores and
+// redoing the same raw staging and im2col; here the window is staged and
+// expanded once, the four waves split the N/16 channel tiles and B comes
+// straight from the (L2-resident, 32 KB) image, so one barrier pair and no
+// weight pass. Same k order, same 32-wide chunks ascending from a zero
+// accumulator: the output is the kernel above's bit for bit.
+extern "C" __global__ __launch_bounds__(256) void fconv_smallc_packed_k(
+    const __hip_bfloat16* __restrict__ in,    // [B,H,W,*] slice
+    int in_stride, int in_off,
+    const __hip_bfloat16* __restrict__ wpk,   // [N][128]
+    const float* __restrict__ bias,
+    __hip_bfloat16* __restrict__ out,         // [B,H,W,N]
+    int H, int W, int C, int N, int kh, int kw, int act, int kchunks) {
+    __shared__ __hip_bfloat16 sraw[9 * 40 * 4];
+    __shared__ __hip_bfloat16 sa[32 * SCM_KP];
+    const int b = blockIdx.y;
+    const int tiles = (W + 31) >> 5;
+    const int y = blockIdx.x / tiles;
+    const int x0 = (blockIdx.x % tiles) << 5;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int kg = lane >> 4;
+    const int l15 = lane & 15;
+    const int aw = 32 + kw - 1;
+    const int pb = kh / 2, pbw = kw / 2;
+    const int K = kh * kw * C;
+    const int Kp = kchunks * 32;
+    const int ntiles = N >> 4;
+    // this wave's B fragments (n-tiles wave, wave+4): issued first, in
+    // flight under the staging
+    short8 bf[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int kc = 0; kc < 4; ++kc) {
+            const int nt = wave + j * 4;
+            short8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (nt < ntiles && kc < kchunks)
+                v = *(const short8*)(wpk + (size_t)(nt * 16 + l15) * 128 +
+                                     kc * 32 + kg * 8);
+            bf[j][kc] = v;
+        }
+    for (int e = tid; e < kh * aw; e += 256) {
+        const int r = e / aw, cx = e % aw;
+        const int yy = y + r - pb, xx = x0 + cx - pbw;
+        const bool ok = (yy >= 0 && yy < H && xx >= 0 && xx < W);
+        const __hip_bfloat16* src =
+            in + (((long long)b * H + yy) * W + xx) * in_stride + in_off;
+        for (int c = 0; c < C; ++c)
+            sraw[e * C + c] = ok ? src[c] : (__hip_bfloat16)0.f;
+    }
+    __syncthreads();
+    for (int e = tid; e < 32 * Kp; e += 256) {
+        const int pos = e / Kp, k = e % Kp;
+        __hip_bfloat16 v = (__hip_bfloat16)0.f;
+        if (k < K) {
+            const int t = k / C, c = k % C;
+            v = sraw[((t / kw) * aw + pos + t % kw) * C + c];
+        }
+        sa[pos * SCM_KP + k] = v;
+    }
+    __syncthreads();
+    floatx4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kc = 0; kc < 4; ++kc) {
+        if (kc >= kchunks) break;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const short8 af = *(const short8*)(
+                sa + (size_t)(i * 16 + l15) * SCM_KP + kc * 32 + kg * 8);
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    af, bf[j][kc], acc[i][j], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int nt = wave + j * 4;
+        if (nt >= ntiles) continue;
+        const int nn = nt * 16 + l15;
+        const float bz = bias ? bias[nn] : 0.0f;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int x = x0 + i * 16 + kg * 4 + r;
+                if (x >= W) continue;
+                float v = acc[i][j][r];
+                if (bias) v += bz;
+                out[(((long long)b * H + y) * W + x) * N + nn] =
+                    (__hip_bfloat16)factivate(v, act);
+            }
+    }
+}
+
+// Serves stride-1 C <= 4, K = taps*C <= 128, N a multiple of 16 up to 128
+// (wpk: the [N][128] image). Returns 0 for anything else.
+extern "C" int launch_fconv_smallc_packed(
+    const void* in, int in_stride, int in_off, const void* wpk,
+    const float* bias, void* out, int B, int H, int W, int C, int N, int kh,
+    int kw, int act, hipStream_t s) {
+    const int taps = kh * kw;
+    if (C < 1 || C > 4 || taps * C > 128 || kh > 9 || kw > 9 || N < 16 ||
+        N > 128 || N % 16 != 0)
+        return 0;
+    const int kchunks = (taps * C + 31) / 32;
+    dim3 grid((unsigned)(H * ((W + 31) / 32)), (unsigned)B);
+    hipLaunchKernelGGL(fconv_smallc_packed_k, grid, dim3(256), 0, s,
+                       (const __hip_bfloat16*)in, in_stride, in_off,
+                       (const __hip_bfloat16*)wpk, bias,
+                       (__hip_bfloat16*)out, H, W, C, N, kh, kw, act,
+                       kchunks);
+    return 1;
+}
+
 // 2D-tile small-C direct conv (stride 1): the per-position window staging
 // above re-reads every overlapped tap (convf1 7x7/C=2: 49 scattered 2-byte
 // loads per output pixel — 43.7 us/call measured). This version stages a
@@ -1395,8 +1531,9 @@ extern "C" void launch_fconv_smallk_nhwc_bf16(
 // ~30 us/iter measured in the chrome trace).
 extern "C" void launch_fconv_dflow_coords(
     const void* in, int Cin, int in_stride, int in_off, const void* wp,
-    const float* bias, const float* coords_in, float* coords_out, int B,
-    int H, int W, int kh, int kw, hipStream_t s) {
+    const float* bias, const float* coords_in, float* coords_out,
+    void* flow_out, int flow_stride, int flow_off, int B, int H, int W,
+    int kh, int kw, hipStream_t s) {
     const long long ncells = (long long)B * H * W;
     if (fconv_tinyn2_ok(fconv_knobs(), Cin, kh, kw)) {
         const int smem = (kh * (8 + kw - 1) * Cin + kh * kw * 2 * Cin) * 2;
@@ -1404,12 +1541,14 @@ extern "C" void launch_fconv_dflow_coords(
         hipLaunchKernelGGL(fconv_tinyn2_k<2>, g2, dim3(256), smem, s,
                            (const __hip_bfloat16*)in, Cin, in_stride,
                            in_off, (const __hip_bfloat16*)wp, bias, nullptr,
-                           coords_in, coords_out, H, W, kh, kw, 0);
+                           coords_in, coords_out, (__hip_bfloat16*)flow_out,
+                           flow_stride, flow_off, H, W, kh, kw, 0);
         return;
     }
     dim3 tg((unsigned)((ncells + 3) / 4));
     hipLaunchKernelGGL(fconv_tinyn_k<2>, tg, dim3(256), 0, s,
                        (const __hip_bfloat16*)in, Cin, in_stride, in_off,
                        (const __hip_bfloat16*)wp, bias, nullptr, coords_in,
-                       coords_out, H, W, kh, kw, 0, ncells);
+                       coords_out, (__hip_bfloat16*)flow_out, flow_stride,
+                       flow_off, H, W, kh, kw, 0, ncells);
 }
